@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: query x gallery NCC pairs/second on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--full] [--dump-outputs DIR]
 
 `--gpus N` (N > 1) invoked plainly starts its own N worker processes (`python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same arguments>`) BEFORE this process has made any GPU call, and
@@ -24,10 +24,17 @@ all pairs, [N > 1: all-gather the score blocks], rank the true matches.
 N > 1: the gallery is sharded (every rank owns G items: weak scaling), queries replicated, one RCCL all-gather of the
 [Q, G] float32 score blocks per step.
 
-The JSON line also carries `roofline` for the dominant kernel (duration from HIP events on the launch stream inside the
-timed region) and, at N = 1, `cpu_baseline`: the CPU oracle ("port" of the reference scorer) timed on the host cores on
-a bounded sample (>= 30 s), run BEFORE this process initialises the GPU (its process pool forks), together with a parity
-check of the GPU's scores and of the full rank vectors of the sampled queries against it.
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the outputs (`--dump-outputs`)
+and the JSON line.  `--full` adds the measurements and checks beyond it.  The line then also carries `roofline` for the
+dominant kernel (duration from HIP events on the launch stream inside the timed region) and, at N = 1, `cpu_baseline`:
+the CPU oracle ("port" of the reference scorer) timed on the host cores on a bounded sample (>= 30 s), run BEFORE this
+process initialises the GPU (its process pool forks), together with a parity check of the GPU's scores and of the full
+rank vectors of the sampled queries against it.  With `--full`, the default one-GPU run also measures config 3 (as
+`secondary`) and configs 2 and 3 time their extractor (`extractor`).
+
+`--dump-outputs DIR` writes what the last timed step computed: `scores.npy` (the [Q, G] float32 score matrix; beyond
+56 MB a fixed seeded sample of its gallery columns, whose indices go to `score_columns.npy`) and `ranks.npy` (the true
+match's rank of every query, as float64).  The inputs are seeded, so the same arguments give the same inputs in every run.
 
 `--emu` (tests only) runs the same step on the CPU emulation of the kernels with a tiny workload and the gloo backend.
 """
@@ -285,6 +292,22 @@ def lib_sha16(path):
     return h.hexdigest()[:16]
 
 
+DUMP_SCORES_LIMIT = 56 << 20  # bytes of scores.npy: with the ranks, the dump stays under 64 MB
+
+
+def dump_outputs(path, scores, ranks):
+    """The outputs of the timed path's last step as .npy files (float32 / float64) under `path`."""
+    os.makedirs(path, exist_ok=True)
+    scores = np.asarray(scores, dtype=np.float32)
+    if scores.nbytes > DUMP_SCORES_LIMIT:
+        keep = max(1, DUMP_SCORES_LIMIT // (4 * scores.shape[0]))
+        cols = np.sort(np.random.default_rng(SEED).choice(scores.shape[1], keep, replace=False))
+        scores = scores[:, cols]
+        np.save(os.path.join(path, "score_columns.npy"), cols.astype(np.float64))
+    np.save(os.path.join(path, "scores.npy"), np.ascontiguousarray(scores))
+    np.save(os.path.join(path, "ranks.npy"), np.asarray(ranks, dtype=np.float64))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     ap = argparse.ArgumentParser()
@@ -300,11 +323,15 @@ def main(argv=None):
     ap.add_argument("--noise", type=int, default=None, help="noise amplitude of the synthetic queries (default: the workload's)")
     ap.add_argument("--no-extractor", action="store_true")
     ap.add_argument("--max-prepared-gib", type=float, default=0.0, help="HBM budget of one prepared gallery chunk (default: automatic)")
-    ap.add_argument("--no-secondary", action="store_true", help="do not append the config-3 measurement to the default run")
+    ap.add_argument("--no-secondary", action="store_true", help="do not append the config-3 measurement to the default --full run")
     ap.add_argument("--cpu-seconds", type=float, default=45.0, help="target duration of the CPU baseline sample")
     ap.add_argument("--cpu-sample-queries", type=int, default=0)
     ap.add_argument("--cpu-sample-gallery", type=int, default=0)
     ap.add_argument("--emu", action="store_true", help="tests: CPU emulation of the kernels, tiny workload, gloo")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline + parity sample, the config-3 secondary, the extractor and the roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's scores and ranks as .npy files to DIR")
     args = ap.parse_args(argv)
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -312,17 +339,17 @@ def main(argv=None):
 
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     rank_env = int(os.environ.get("RANK", "0"))
-    # The default one-GPU run of the headline workload also measures BASELINE config 3 (the bf16 small-map workload of the
-    # matrix-core scorer) and appends it as `secondary`: the same step, its own roofline / cpu_baseline / parity_sample.
+    # The default one-GPU --full run of the headline workload also measures BASELINE config 3 (the bf16 small-map workload of
+    # the matrix-core scorer) and appends it as `secondary`: the same step, its own roofline / cpu_baseline / parity_sample.
     configs = [args.config]
-    if (args.config == 2 and world_env == 1 and not args.emu and not args.no_secondary and not args.queries
+    if (args.full and args.config == 2 and world_env == 1 and not args.emu and not args.no_secondary and not args.queries
             and not args.gallery_per_gpu and args.method == "auto"):
         configs.append(3)
 
     # ---- CPU baseline legs first: before torch touches the GPU (fork-safe), rank 0 of a one-GPU job only ---------
     cores, cores_how = usable_cores()
     cpu_legs = {}
-    if world_env == 1 and rank_env == 0 and not args.no_cpu_baseline and not args.emu:
+    if args.full and world_env == 1 and rank_env == 0 and not args.no_cpu_baseline and not args.emu:
         for cfg in configs:
             set_noise(args, cfg)
             wl, layer_shapes, nq, ng_local = workload_sizes(args, cfg, cfg == args.config)
@@ -451,11 +478,11 @@ def run_config(args, config_id, ctx, cpu, primary):
         for start in range(0, ng_local, chunk):
             n = min(chunk, ng_local - start)
             scorer.prepare_gallery(plan, dev.narrow0(g, start, n), out=pg)
-            if record and k == 0:
+            if record and k == 0 and args.full:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
             scorer.score_prepared(plan, pq, nq, pg, n, out, ng_local, start)
-            if record and k == 0:
+            if record and k == 0 and args.full:
                 e1.record()
                 pair_events.append((e0, e1, nq * n))
 
@@ -498,7 +525,7 @@ def run_config(args, config_id, ctx, cpu, primary):
     for _ in range(args.warmup):
         step(False)
     sampler = None
-    if rank == 0 and not args.emu:
+    if args.full and rank == 0 and not args.emu:
         try:
             pr = torch.cuda.get_device_properties(local)
             sampler = ClockSampler(f"{pr.pci_domain_id:04x}:{pr.pci_bus_id:02x}:{pr.pci_device_id:02x}.0")
@@ -519,6 +546,8 @@ def run_config(args, config_id, ctx, cpu, primary):
     pairs_per_step = nq * ng_total
     value = pairs_per_step * args.steps / dt
     ranks = dev.to_host(ranks_dev)
+    if primary and rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dev.to_host(full), ranks)
 
     # ---- N > 1: what the collective saw, and proof that every rank ended up with the same [Q, G] matrix ----------------------
     collective = None
@@ -655,7 +684,7 @@ def run_config(args, config_id, ctx, cpu, primary):
     if args.emu:
         out["data"] = "synthetic (CPU emulation of the kernels: test mode, not a measurement)"
 
-    if rank == 0 and not args.no_extractor and not args.emu and config_id in (2, 3):
+    if args.full and rank == 0 and not args.no_extractor and not args.emu and config_id in (2, 3):
         # the extractor, reported separately: images/s on 512x256 prints with seeded synthetic weights, in the
         # reference's float32 arithmetic (the f32 matrix cores) and on the 16-bit matrix cores (bfloat16 operands, f32 sums)
         from shoeprint_image_retrieval_amd import network

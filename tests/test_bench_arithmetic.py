@@ -39,3 +39,18 @@ def test_matrix_core_form_flops():
     assert abs(2.0 * (28 * 16) * 336 * 1024 / 1e9 - 0.3083) < 1e-4
     assert bench.PEAK_BF16_TFLOPS == 2500.0
     assert bench.mfma_tile_steps(28, 12) == (231, 294)  # 63 of the 294 tile steps fall on all-zero fragments
+
+
+def test_dump_outputs_samples_a_large_score_matrix(tmp_path, monkeypatch):
+    import numpy as np
+
+    monkeypatch.setattr(bench, "DUMP_SCORES_LIMIT", 3 * 4 * 10)  # room for 10 of the 50 columns of 3 rows
+    scores = np.arange(150, dtype=np.float32).reshape(3, 50)
+    bench.dump_outputs(str(tmp_path), scores, np.array([1, 2, 3], np.int32))
+    cols = np.load(tmp_path / "score_columns.npy")
+    got = np.load(tmp_path / "scores.npy")
+    assert got.dtype == np.float32 and got.shape == (3, 10) and cols.dtype == np.float64
+    assert np.all(np.diff(cols) > 0)
+    np.testing.assert_array_equal(got, scores[:, cols.astype(np.int64)])
+    bench.dump_outputs(str(tmp_path / "again"), scores, np.array([1, 2, 3], np.int32))
+    np.testing.assert_array_equal(np.load(tmp_path / "again" / "score_columns.npy"), cols)  # a fixed, seeded sample

@@ -40,6 +40,23 @@ def test_plain_gpus2_invocation_starts_its_own_workers_and_matches_one_process()
     assert len(col["matrix_digest"]) == 16
 
 
+def test_dump_outputs_writes_the_last_steps_scores_and_ranks(tmp_path):
+    import numpy as np
+
+    one = run_bench("--gallery-per-gpu", "12", "--steps", "2", "--dump-outputs", str(tmp_path / "a"))
+    run_bench("--gallery-per-gpu", "12", "--dump-outputs", str(tmp_path / "b"))
+    assert one["steps"] == 2 and one["ms_per_step"] > 0
+    assert not {"roofline", "cpu_baseline", "parity_sample", "secondary", "extractor"} & set(one)  # those need --full
+    assert sorted(os.listdir(tmp_path / "a")) == ["ranks.npy", "scores.npy"]
+    scores, ranks = np.load(tmp_path / "a" / "scores.npy"), np.load(tmp_path / "a" / "ranks.npy")
+    assert scores.dtype == np.float32 and scores.shape == (4, 12)
+    assert ranks.dtype == np.float64 and ranks.shape == (4,) and np.all(ranks >= 1)
+    assert abs(float(np.mean(ranks)) - one["mean_rank"]) < 0.01
+    # the inputs are seeded: a second run computes the same outputs
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "scores.npy"), scores)
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "ranks.npy"), ranks)
+
+
 @pytest.mark.parametrize("config", [3, 4, 5])
 def test_other_configs_step(config):
     out = run_bench("--config", str(config), "--gallery-per-gpu", "5")

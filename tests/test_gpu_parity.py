@@ -269,7 +269,7 @@ def test_bench_step_on_chunked_fp16_gallery(config):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     gib = 0.45 if config == 4 else 1.35  # 28.7 MB per prepared conv3_3 item (config 5: a third of the budget per layer)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--config", str(config), "--steps", "1", "--warmup", "0",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--config", str(config), "--steps", "1", "--warmup", "0",
            "--queries", "6", "--gallery-per-gpu", "40", "--max-prepared-gib", str(gib), "--no-extractor",
            "--cpu-sample-queries", "4", "--cpu-sample-gallery", "10"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)

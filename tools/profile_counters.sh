@@ -11,6 +11,6 @@ for ctr in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS" \
            "SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA" \
            "TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
-  timeout -k 10 240 rocprofv3 --pmc $ctr --output-format csv -d $OUT/p$i -o x -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-parity-sample > $OUT/p$i.log 2>&1 || { echo "pass $i failed"; tail -5 $OUT/p$i.log; exit 1; }
+  timeout -k 10 240 rocprofv3 --pmc $ctr --output-format csv -d $OUT/p$i -o x -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-parity-sample > $OUT/p$i.log 2>&1 || { echo "pass $i failed"; tail -5 $OUT/p$i.log; exit 1; }
 done
 echo done

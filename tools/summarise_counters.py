@@ -37,7 +37,7 @@ def main():
             derived["l2_hit_rate"] = round(c["TCC_HIT_sum"] / (c["TCC_HIT_sum"] + c["TCC_MISS_sum"]), 4)
         out[k] = {"per_dispatch": {a: c[a] for a in sorted(c)}, "derived": derived}
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", f"{tag}_sq_counters.json")
-    json.dump({"command": "rocprofv3 --pmc <group> -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-parity-sample "
+    json.dump({"command": "rocprofv3 --pmc <group> -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-parity-sample "
                           "(one pass per counter group, tools/profile_counters.sh)", "kernels": out}, open(path, "w"), indent=1)
     for k, v in out.items():
         print(k, v["derived"])
