@@ -289,6 +289,18 @@ size_t spr_resnet_workspace_bytes(const spr_resnet_plan* plan, int64_t n, int32_
 int spr_resnet_forward(spr_resnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
                        int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
                        float* out, spr_stream_t stream);
+/* Per-layer trace of a 16-bit plan (f32 plans: SPR_ERR_UNSUPPORTED), for tests: spr_*_forward_trace is the plain forward
+ * (the same kernels, the same result in `out`) that also copies, behind every layer and on the same stream, what that layer
+ * stored into the device buffer `trace`.  spr_*_trace_layout(plan, n, in_h, in_w, records, total_bytes) returns the number of
+ * records and, where the pointers are not null, int64 records[6 * i ..] = byte offset into `trace`, h, w, channels, element
+ * type (SPR_F16 | SPR_BF16 | SPR_F32), layout (0 NHWC: [n][h][w][channels], padded channels included; 1 NCHW: the float32
+ * output of the last layer, real channels) and the size of `trace` in bytes.  ResNet records: the stem's output before the
+ * max pool, the max pool's output, then one per convolution of spr_resnet_conv_shape's list, in that (conv index) order. */
+int spr_resnet_trace_layout(const spr_resnet_plan* plan, int64_t n, int32_t in_h, int32_t in_w, int64_t* records,
+                            size_t* total_bytes);
+int spr_resnet_forward_trace(spr_resnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                             int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
+                             float* out, void* trace, spr_stream_t stream);
 
 /* ------------------------------------------------------------------ EfficientNetV2 feature extractor
  * network.py:163-175 (model choice), :185-186 (`list(model.features.children())[:block]`), :60-71 / :74-87 (transforms).
@@ -324,6 +336,14 @@ size_t spr_effnet_workspace_bytes(const spr_effnet_plan* plan, int64_t n, int32_
 int spr_effnet_forward(spr_effnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
                        int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
                        float* out, spr_stream_t stream);
+/* Per-layer trace (see spr_resnet_forward_trace), one record per layer of the plan in order: the stem and every convolution /
+ * depthwise convolution as stored (16-bit NHWC, cout_p channels), a squeeze-excitation's float32 factors [n][cin_p] (h = w =
+ * 1), the last layer's float32 NCHW output. */
+int spr_effnet_trace_layout(const spr_effnet_plan* plan, int64_t n, int32_t in_h, int32_t in_w, int64_t* records,
+                            size_t* total_bytes);
+int spr_effnet_forward_trace(spr_effnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                             int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
+                             float* out, void* trace, spr_stream_t stream);
 
 /* ------------------------------------------------------------------ DenseNet_201 feature extractor
  * network.py:176-179, :185-186: torchvision's densenet201 `features` = [conv0, norm0, relu0, pool0, denseblock1, transition1,

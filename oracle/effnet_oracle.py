@@ -12,6 +12,8 @@ PARITY UNPINNED by the reference: network.py needs cv2, torchvision and download
 
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -123,7 +125,7 @@ def get_feature_maps(img: np.ndarray, ops, parameters, mean, std, bn_eps: float 
     s = torch.tensor(std, dtype=torch.float32)[:, None, None]
     x = ((x - m) / s)[None]
     block_in, scale = x, None
-    if compute:
+    if compute:  # a loop over step16 / se_step: the per-layer reference of tests/layer_cases.py
         return _forward16(x, ops, parameters, bn_eps, compute)
     with torch.no_grad():
         for op, p in zip(ops, parameters):
@@ -149,35 +151,93 @@ def get_feature_maps(img: np.ndarray, ops, parameters, mean, std, bn_eps: float 
     return x.numpy().squeeze(0)
 
 
+class Step(NamedTuple):
+    """One layer restated: y = act(pre) (+ res); A, K: see step16."""
+    y: torch.Tensor
+    A: torch.Tensor
+    K: int
+    pre: torch.Tensor
+    res: torch.Tensor | None
+
+
+def fold16(op, p, bn_eps, compute):
+    """(weights, bias) of a convolution / depthwise layer as a 16-bit plan uses them, float32 tensors: eval-mode BatchNorm folded
+    in float32 as the library folds it; THEN a convolution's weights rounded to the compute type (depthwise weights stay f32)."""
+    w, b, gamma, beta, mu, var = (np.asarray(a, dtype=np.float32) for a in p)
+    s = gamma / np.sqrt(var + np.float32(bn_eps))
+    wf = torch.from_numpy(np.ascontiguousarray(w * s[:, None, None, None]))
+    bf = torch.from_numpy(np.ascontiguousarray((b - mu) * s + beta))
+    return (_round(wf, compute) if op["kind"] == 0 else wf), bf
+
+
+def operand16(x, scale, compute):
+    """A convolution's operand: the stored input, or round(x * factor) with the product in float32 where a squeeze-excitation
+    scales it (scale: [N, C, 1, 1] float32 factors)."""
+    return x if scale is None else _round(x * scale, compute)
+
+
+def se_step(op, p, x, dtype=torch.float32, bound=False):
+    """Squeeze-excitation factors [N, C, 1, 1] of the stored tensor x: mean, fc1, SiLU, fc2, sigmoid, evaluated in ``dtype``.
+    bound=True also returns E: an absolute bound on the float32 evaluation's error (the kernels' f32 chains, worst case:
+    enet_pool16_kernel's 32 strided chains + their sum, enet_fc1_kernel's two fma chains + 7 adds, enet_fc2_kernel's four
+    chains + 3 adds; SiLU's slope <= 1.1, the sigmoid's <= 1/4, a few units of rounding for each of them)."""
+    t = [torch.from_numpy(np.asarray(a, dtype=np.float32)).to(dtype) for a in p]
+    x = x.to(dtype)
+    with torch.no_grad():
+        z = x.mean(dim=(2, 3), keepdim=True)
+        z = F.silu(F.conv2d(z, t[0].reshape(op["sq"], op["cin"], 1, 1), t[1]))
+        f = torch.sigmoid(F.conv2d(z, t[2].reshape(op["cin"], op["sq"], 1, 1), t[3]))
+        if not bound:
+            return f
+        u, hw, c, sq = 2.0 ** -24, x.shape[2] * x.shape[3], op["cin"], op["sq"]
+        a = [v.abs() for v in t]
+        pm = x.abs().mean(dim=(2, 3), keepdim=True)
+        e_p = (-(-hw // 32) + 34) * u * pm
+        mz = F.conv2d(pm, a[0].reshape(sq, c, 1, 1), a[1])
+        e_z = (-(-c // 128) + 9) * u * mz + F.conv2d(e_p, a[0].reshape(sq, c, 1, 1))
+        e_h = 1.1 * e_z + 4 * u * z.abs()
+        mt = F.conv2d(z.abs(), a[2].reshape(c, sq, 1, 1), a[3])
+        e_t = (-(-sq // 4) + 4) * u * mt + F.conv2d(e_h, a[2].reshape(c, sq, 1, 1))
+        return f, 1.05 * (0.25 * e_t + 4 * u * f)
+
+
+def step16(op, p, x, block_in, scale, bn_eps, compute, dtype=torch.float32, bound=False):
+    """One convolution / depthwise layer of a 16-bit plan from its inputs: x the stored (rounded) input [N, C, H, W], block_in
+    the stored block input (the residual operand, used where op["res"]), scale the squeeze-excitation factors on the operand or
+    None.  Returns the layer's value BEFORE it is stored (the caller rounds it, or not for the last layer), evaluated in
+    ``dtype``: float32 = the end-to-end oracle's arithmetic, float64 = the exact value of the layer.  The operand is always
+    prepared in float32 (round(x * factor) is a float32 product).  bound=True returns a Step: y, A = |W| * |a| + |b| (+ |res|)
+    (the magnitude sum that scales the kernel's f32 error), K (the reduction length, cin x taps; depthwise: taps), and the parts
+    y is made of: pre (convolution + bias, before the activation) and res (the residual operand or None)."""
+    wf, bf = fold16(op, p, bn_eps, compute)
+    a = operand16(x, scale, compute) if op["kind"] == 0 else x
+    groups = op["cin"] if op["kind"] == 1 else 1
+    cv = dict(stride=op["stride"], padding=op["ks"] // 2, groups=groups)
+    res = block_in.to(dtype) if op["kind"] == 0 and op["res"] else None
+    with torch.no_grad():
+        pre = F.conv2d(a.to(dtype), wf.to(dtype), bf.to(dtype), **cv)
+        y = F.silu(pre) if op["act"] == 2 else pre
+        if res is not None:
+            y = y + res
+        if not bound:
+            return y
+        A = F.conv2d(a.to(torch.float64).abs(), wf.to(torch.float64).abs(), bf.to(torch.float64).abs(), **cv)
+        if res is not None:
+            A = A + res.abs()
+        return Step(y, A, (op["cin"] if op["kind"] == 0 else 1) * op["ks"] ** 2, pre, res)
+
+
 def _forward16(x, ops, parameters, bn_eps, compute):
     x = _round(x, compute)  # the stored tensor: what the next layer reads
     block_in, scale = x, None
-    with torch.no_grad():
-        for i, (op, p) in enumerate(zip(ops, parameters)):
-            last = i + 1 == len(ops)
-            t = [np.asarray(a, dtype=np.float32) for a in p]
-            if op["kind"] == 2:
-                z = x.mean(dim=(2, 3), keepdim=True)
-                z = F.silu(F.conv2d(z, torch.from_numpy(t[0].reshape(op["sq"], op["cin"], 1, 1)), torch.from_numpy(t[1])))
-                scale = torch.sigmoid(F.conv2d(z, torch.from_numpy(t[2].reshape(op["cin"], op["sq"], 1, 1)), torch.from_numpy(t[3])))
-                continue
-            w, b, gamma, beta, mu, var = t
-            s = gamma / np.sqrt(var + np.float32(bn_eps))  # eval-mode BatchNorm folded as the library folds it (float32)
-            wf = torch.from_numpy(np.ascontiguousarray(w * s[:, None, None, None]))
-            bf = torch.from_numpy(np.ascontiguousarray((b - mu) * s + beta))
-            a = x
-            if op["kind"] == 0:
-                if scale is not None:
-                    a = _round(a * scale, compute)
-                    scale = None
-                wf = _round(wf, compute)
-            groups = op["cin"] if op["kind"] == 1 else 1
-            y = F.conv2d(a, wf, bf, stride=op["stride"], padding=op["ks"] // 2, groups=groups)
-            if op["act"] == 2:
-                y = F.silu(y)
-            if op["kind"] == 0 and op["res"]:
-                y = y + block_in
-            x = y if last else _round(y, compute)
-            if op["block_end"]:
-                block_in = x
+    for i, (op, p) in enumerate(zip(ops, parameters)):
+        if op["kind"] == 2:
+            scale = se_step(op, p, x)
+            continue
+        y = step16(op, p, x, block_in, scale if op["kind"] == 0 else None, bn_eps, compute)
+        if op["kind"] == 0:
+            scale = None
+        x = y if i + 1 == len(ops) else _round(y, compute)
+        if op["block_end"]:
+            block_in = x
     return x.numpy().squeeze(0)

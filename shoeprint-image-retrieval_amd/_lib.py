@@ -99,6 +99,9 @@ SIGNATURES = {
     "spr_effnet_workspace_bytes": (_SZ, [_VP, _I64, _I32, _I32]),
     "spr_effnet_forward": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                      _VP, _VP, _VP, _VP]),
+    "spr_effnet_trace_layout": (C.c_int, [_VP, _I64, _I32, _I32, C.POINTER(_I64), C.POINTER(_SZ)]),
+    "spr_effnet_forward_trace": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           _VP, _VP, _VP, _VP, _VP]),
     "spr_resnet_plan_create": (C.c_int, [_I32, C.POINTER(_VP)]),
     "spr_resnet_plan_create_ex": (C.c_int, [_I32, _I32, C.POINTER(_VP)]),
     "spr_resnet_plan_compute": (C.c_int, [_VP]),
@@ -111,6 +114,9 @@ SIGNATURES = {
     "spr_resnet_workspace_bytes": (_SZ, [_VP, _I64, _I32, _I32]),
     "spr_resnet_forward": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                      _VP, _VP, _VP, _VP]),
+    "spr_resnet_trace_layout": (C.c_int, [_VP, _I64, _I32, _I32, C.POINTER(_I64), C.POINTER(_SZ)]),
+    "spr_resnet_forward_trace": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           _VP, _VP, _VP, _VP, _VP]),
     "spr_synth_gallery": (C.c_int, [_VP, _I64, _I64, _I32, _I32, _I32, C.c_uint64, _VP]),
     "spr_synth_queries": (C.c_int, [_VP, _I64, _I64, _VP, _I32, _I32, _I32, C.c_uint64, _I32, _I32, _I32, _VP]),
 }

@@ -1099,9 +1099,78 @@ static int launch_gemm16(int kind, const RConv& c, const uint16_t* in, int64_t n
   return check_launch("conv_gemm16_kernel");
 }
 
-// the bottlenecks of a 16-bit plan: x (the pooled stem output, 16-bit NHWC) lives in buf[0]; t1 / t2 / y in buf[1..3]
+// ---- trace records (spr_*_forward_trace): what a layer stored, copied device to device behind it on the same stream.
+// Records lie 256-byte aligned in plan order; 16-bit NHWC [n][h][w][c] (c padded as stored), float32 [n][c] (squeeze-
+// excitation factors: h = w = 1) or the float32 NCHW output [n][c][h][w] of the last layer (c real).
+namespace {
+struct TraceRec { size_t off, bytes; int h, w, c, dtype, nchw; };
+struct TraceLayout {
+  std::vector<TraceRec> recs;
+  size_t total = 0;
+  int64_t n = 0;
+  void add(int h, int w, int c, int dtype, int nchw) {
+    const size_t bytes = static_cast<size_t>(n) * h * w * c * (dtype == SPR_F32 ? 4 : 2);
+    recs.push_back(TraceRec{total, bytes, h, w, c, dtype, nchw});
+    total += align_up(bytes, 256);
+  }
+};
+// copy record i from src (a null trace: the plain forward, nothing to do)
+int trace_copy(unsigned char* trace, const TraceLayout* lay, size_t i, const void* src, hipStream_t s) {
+  if (!trace) return SPR_OK;
+  const TraceRec& r = lay->recs[i];
+  if (hipMemcpyAsync(trace + r.off, src, r.bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+    set_error("spr_*_forward_trace: copy of record %zu failed", i);
+    return SPR_ERR_HIP;
+  }
+  return SPR_OK;
+}
+int trace_query(const TraceLayout& lay, int64_t* records, size_t* total_bytes) {
+  if (records)
+    for (size_t i = 0; i < lay.recs.size(); ++i) {
+      const TraceRec& r = lay.recs[i];
+      const int64_t v[6] = {static_cast<int64_t>(r.off), r.h, r.w, r.c, r.dtype, r.nchw};
+      for (int k = 0; k < 6; ++k) records[6 * i + k] = v[k];
+    }
+  if (total_bytes) *total_bytes = lay.total;
+  return static_cast<int>(lay.recs.size());
+}
+}  // namespace
+
+// stem (before pooling), max pool, then one record per convolution in conv index order (c1, c2, c3, [downsample])
+static TraceLayout resnet_trace_layout(const spr_resnet_plan* plan, int64_t n, int in_h, int in_w) {
+  TraceLayout lay;
+  lay.n = n;
+  int h = (in_h + 1) / 2, w = (in_w + 1) / 2;
+  lay.add(h, w, 64, plan->compute, 0);
+  h = (h + 1) / 2; w = (w + 1) / 2;
+  lay.add(h, w, 64, plan->compute, 0);
+  size_t i = 1;
+  while (i < plan->convs.size()) {
+    const bool down = plan->convs[i + 2].res == 2;
+    const bool last = i + (down ? 4 : 3) == plan->convs.size();
+    const int ho = plan->convs[i + 1].stride == 2 ? (h + 1) / 2 : h, wo = plan->convs[i + 1].stride == 2 ? (w + 1) / 2 : w;
+    lay.add(h, w, plan->convs[i].cout, plan->compute, 0);
+    lay.add(ho, wo, plan->convs[i + 1].cout, plan->compute, 0);
+    if (last) lay.add(ho, wo, plan->convs[i + 2].cout, SPR_F32, 1);
+    else lay.add(ho, wo, plan->convs[i + 2].cout, plan->compute, 0);
+    if (down) lay.add(ho, wo, plan->convs[i + 3].cout, plan->compute, 0);
+    h = ho; w = wo;
+    i += down ? 4 : 3;
+  }
+  return lay;
+}
+
+extern "C" int spr_resnet_trace_layout(const spr_resnet_plan* plan, int64_t n, int32_t in_h, int32_t in_w, int64_t* records,
+                                       size_t* total_bytes) {
+  if (!plan || n < 0 || in_h < 32 || in_w < 32) { set_error("spr_resnet_trace_layout: bad argument"); return SPR_ERR_ARG; }
+  if (plan->compute == SPR_F32) { set_error("spr_resnet_trace_layout: 16-bit plans only"); return SPR_ERR_UNSUPPORTED; }
+  return trace_query(resnet_trace_layout(plan, n, in_h, in_w), records, total_bytes);
+}
+
+// the bottlenecks of a 16-bit plan: x (the pooled stem output, 16-bit NHWC) lives in buf[0]; t1 / t2 / y in buf[1..3].
+// trace / lay: null, or where every convolution's stored result is copied (record 1 + conv index)
 static int resnet_blocks16(const spr_resnet_plan* plan, int64_t n, int h, int w, const float* pk, uint16_t* const buf[4],
-                           float* out, hipStream_t s) {
+                           float* out, hipStream_t s, unsigned char* trace, const TraceLayout* lay) {
   uint16_t* x = buf[0];
   uint16_t* t1 = buf[1];
   uint16_t* t2 = buf[2];
@@ -1116,20 +1185,24 @@ static int resnet_blocks16(const spr_resnet_plan* plan, int64_t n, int h, int w,
     const bool last = i + (down ? 4 : 3) == plan->convs.size();
     const int ho = c2.stride == 2 ? (h + 1) / 2 : h, wo = c2.stride == 2 ? (w + 1) / 2 : w;
     int rc = launch_gemm16<1, 1>(kind, c1, x, n, h, w, pk, nullptr, t1, nullptr, s);
+    if (rc == SPR_OK) rc = trace_copy(trace, lay, 1 + i, t1, s);
     if (rc != SPR_OK) return rc;
     rc = c2.stride == 2 ? launch_gemm16<3, 2>(kind, c2, t1, n, h, w, pk, nullptr, t2, nullptr, s)
                         : launch_conv16_3x3(kind, t1, n, h, w, c2.cin, c2.cout, reinterpret_cast<const uint16_t*>(pk + c2.w_off),
                                             pk + c2.b_off, c2.relu, t2, s);
+    if (rc == SPR_OK) rc = trace_copy(trace, lay, 2 + i, t2, s);
     if (rc != SPR_OK) return rc;
     const uint16_t* resid = x;
     if (down) {
       const RConv& cd = plan->convs[i + 3];
       rc = cd.stride == 2 ? launch_gemm16<1, 2>(kind, cd, x, n, h, w, pk, nullptr, t1, nullptr, s)
                           : launch_gemm16<1, 1>(kind, cd, x, n, h, w, pk, nullptr, t1, nullptr, s);
+      if (rc == SPR_OK) rc = trace_copy(trace, lay, 4 + i, t1, s);
       if (rc != SPR_OK) return rc;
       resid = t1;
     }
     rc = launch_gemm16<1, 1>(kind, c3, t2, n, ho, wo, pk, resid, y, last ? out : nullptr, s);
+    if (rc == SPR_OK) rc = trace_copy(trace, lay, 3 + i, last ? static_cast<const void*>(out) : y, s);
     if (rc != SPR_OK) return rc;
     h = ho; w = wo;
     uint16_t* old = x;
@@ -1153,9 +1226,9 @@ static int launch_gemm(const RConv& c, const float* in, int64_t n, int h, int w,
   return check_launch("conv_gemm_kernel");
 }
 
-extern "C" int spr_resnet_forward(spr_resnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
-                                  int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
-                                  void* workspace, float* out, spr_stream_t stream) {
+static int resnet_forward(spr_resnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                          int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
+                          float* out, spr_stream_t stream, unsigned char* trace) {
   if (!plan) { set_error("spr_resnet_forward: null plan"); return SPR_ERR_ARG; }
   if (n < 0 || n > 65535 || in_h < 32 || in_w < 32 || (in_channels != 1 && in_channels != 3)) {
     set_error("spr_resnet_forward: bad sizes (n in [0, 65535], images at least 32 x 32, in_channels 1 or 3)");
@@ -1176,6 +1249,8 @@ extern "C" int spr_resnet_forward(spr_resnet_plan* plan, const uint8_t* images, 
     for (int i = 0; i < 4; ++i)
       b16[i] = reinterpret_cast<uint16_t*>(static_cast<unsigned char*>(workspace) + stem_bytes + i * resnet_big16_bytes(n, in_h, in_w));
   }
+  TraceLayout lay;
+  if (trace) lay = resnet_trace_layout(plan, n, in_h, in_w);
   // stem + max pool
   int h = (in_h + 1) / 2, w = (in_w + 1) / 2;
   {
@@ -1197,6 +1272,7 @@ extern "C" int spr_resnet_forward(spr_resnet_plan* plan, const uint8_t* images, 
                            mean3[1], mean3[2], inv_std3[0], inv_std3[1], inv_std3[2], w16, pk + c.b_off, o16, 1);
     }
     int rc = check_launch("stem_kernel");
+    if (rc == SPR_OK) rc = trace_copy(trace, &lay, 0, buf[1], s);
     if (rc != SPR_OK) return rc;
     const int hp = (h + 1) / 2, wp = (w + 1) / 2;
     const size_t total = static_cast<size_t>(n) * hp * wp * 64;
@@ -1210,10 +1286,11 @@ extern "C" int spr_resnet_forward(spr_resnet_plan* plan, const uint8_t* images, 
                          b16[0], total / 8);
     }
     rc = check_launch("maxpool3_kernel");
+    if (rc == SPR_OK) rc = trace_copy(trace, &lay, 1, b16[0], s);
     if (rc != SPR_OK) return rc;
     h = hp; w = wp;
   }
-  if (!f32) return resnet_blocks16(plan, n, h, w, pk, b16, out, s);
+  if (!f32) return resnet_blocks16(plan, n, h, w, pk, b16, out, s, trace, trace ? &lay : nullptr);
   // bottlenecks: x = buf[0]
   float* x = buf[0];
   float* t1 = buf[1];
@@ -1250,6 +1327,21 @@ extern "C" int spr_resnet_forward(spr_resnet_plan* plan, const uint8_t* images, 
     i += down ? 4 : 3;
   }
   return SPR_OK;
+}
+
+extern "C" int spr_resnet_forward(spr_resnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                                  int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
+                                  void* workspace, float* out, spr_stream_t stream) {
+  return resnet_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, stream, nullptr);
+}
+
+extern "C" int spr_resnet_forward_trace(spr_resnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                                        int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
+                                        void* workspace, float* out, void* trace, spr_stream_t stream) {
+  if (!plan || !trace) { set_error("spr_resnet_forward_trace: null pointer"); return SPR_ERR_ARG; }
+  if (plan->compute == SPR_F32) { set_error("spr_resnet_forward_trace: 16-bit plans only"); return SPR_ERR_UNSUPPORTED; }
+  return resnet_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, stream,
+                        static_cast<unsigned char*>(trace));
 }
 
 // ================================================================ EfficientNetV2 truncations (network.py:163-175, :185-186)
@@ -1303,6 +1395,7 @@ struct spr_effnet_plan {
   std::vector<EOp> ops;
   size_t packed_floats;
   int max_expand_p;  // widest expanded tensor (squeeze-excitation scratch)
+  int max_sq;        // widest squeeze-excitation hidden layer (its scratch)
 };
 
 extern "C" int spr_effnet_plan_create(int32_t arch, int32_t block, spr_effnet_plan** plan_out) {
@@ -1342,7 +1435,7 @@ extern "C" int spr_effnet_plan_create_ex(int32_t arch, int32_t block, int32_t co
   }
   spr_effnet_plan* plan = new (std::nothrow) spr_effnet_plan();
   if (!plan) { set_error("out of host memory"); return SPR_ERR_ARG; }
-  plan->arch = arch; plan->block = block; plan->max_expand_p = 64; plan->compute = compute;
+  plan->arch = arch; plan->block = block; plan->max_expand_p = 64; plan->max_sq = 1; plan->compute = compute;
   size_t off = 0;
   auto take = [&](size_t n) { const size_t o = off; off += (n + 3) / 4 * 4; return o; };
   auto conv = [&](int cin, int cout, int ks, int stride, int act, int res, int scaled, int end, int feature, int cin_p) {
@@ -1383,6 +1476,7 @@ extern "C" int spr_effnet_plan_create_ex(int32_t arch, int32_t block, int32_t co
         e.b2_off = take(e.cin_p);
         plan->ops.push_back(e);
         if (e.cin_p > plan->max_expand_p) plan->max_expand_p = e.cin_p;
+        if (e.sq > plan->max_sq) plan->max_sq = e.sq;
         conv(exp, g.cout, 1, 1, 0, res, 1, 1, st + 1, pad64(exp));
       }
     }
@@ -1451,7 +1545,30 @@ extern "C" size_t spr_effnet_workspace_bytes(const spr_effnet_plan* plan, int64_
   const size_t buf = align_up(effnet_buf_floats(plan, n, in_h, in_w) * sizeof(float), 256);
   // four activation buffers, the squeeze-excitation means and factors, and the hidden units of its first layer
   return 4 * buf + 2 * align_up(static_cast<size_t>(n) * plan->max_expand_p * sizeof(float), 256) +
-         align_up(static_cast<size_t>(n) * 256 * sizeof(float), 256);
+         align_up(static_cast<size_t>(n) * plan->max_sq * sizeof(float), 256);
+}
+
+// one record per layer in plan order: the stem and every convolution / depthwise convolution as stored (16-bit NHWC, cout_p
+// channels), a squeeze-excitation's float32 factors [n][cin_p], the last layer's float32 NCHW output
+static TraceLayout effnet_trace_layout(const spr_effnet_plan* plan, int64_t n, int in_h, int in_w) {
+  TraceLayout lay;
+  lay.n = n;
+  int h = in_h, w = in_w;
+  for (size_t i = 0; i < plan->ops.size(); ++i) {
+    const EOp& o = plan->ops[i];
+    if (o.kind == 2) { lay.add(1, 1, o.cin_p, SPR_F32, 0); continue; }
+    if (o.stride == 2) { h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
+    if (i + 1 == plan->ops.size()) lay.add(h, w, o.cout, SPR_F32, 1);
+    else lay.add(h, w, o.cout_p, plan->compute, 0);
+  }
+  return lay;
+}
+
+extern "C" int spr_effnet_trace_layout(const spr_effnet_plan* plan, int64_t n, int32_t in_h, int32_t in_w, int64_t* records,
+                                       size_t* total_bytes) {
+  if (!plan || n < 0 || in_h < 32 || in_w < 32) { set_error("spr_effnet_trace_layout: bad argument"); return SPR_ERR_ARG; }
+  if (plan->compute == SPR_F32) { set_error("spr_effnet_trace_layout: 16-bit plans only"); return SPR_ERR_UNSUPPORTED; }
+  return trace_query(effnet_trace_layout(plan, n, in_h, in_w), records, total_bytes);
 }
 
 template <int KS, int STRIDE>
@@ -1471,10 +1588,13 @@ static int launch_egemm(const EOp& o, const float* in, int64_t n, int h, int w, 
 // channels, the same four buffers: the f32 sizes are kept, half of each is used), the stem on stem16_kernel's 3x3 / stride 2
 // instance, every other convolution on conv_gemm16_kernel (SiLU in front of the residual sum, squeeze-excitation factors on
 // the operand), depthwise convolutions and the squeeze-excitation mean on their 16-bit kernels; float32 NCHW out.
+// trace: null, or where every layer's stored result is copied (effnet_trace_layout)
 static int effnet_forward16(const spr_effnet_plan* plan, const uint8_t* images, int64_t n, int in_h, int in_w, int in_channels,
                             const float* mean3, const float* inv_std3, const float* pk, unsigned char* ws, size_t buf_bytes,
-                            float* out, hipStream_t s) {
+                            float* out, hipStream_t s, unsigned char* trace) {
   const int kind = plan->compute;
+  TraceLayout lay;
+  if (trace) lay = effnet_trace_layout(plan, n, in_h, in_w);
   uint16_t* x = reinterpret_cast<uint16_t*>(ws);
   uint16_t* t1 = reinterpret_cast<uint16_t*>(ws + buf_bytes);
   uint16_t* t2 = reinterpret_cast<uint16_t*>(ws + 2 * buf_bytes);
@@ -1497,6 +1617,7 @@ static int effnet_forward16(const spr_effnet_plan* plan, const uint8_t* images, 
       hipLaunchKernelGGL(HIP_KERNEL_NAME(stem16_kernel<SPR_BF16, 3, 2>), sgrid, dim3(kThreads), 0, s, images, h, w, in_channels,
                          mean3[0], mean3[1], mean3[2], inv_std3[0], inv_std3[1], inv_std3[2], w16, pk + o.b_off, x, 2);
     rc = check_launch("stem16_kernel");
+    if (rc == SPR_OK) rc = trace_copy(trace, &lay, 0, x, s);
     if (rc != SPR_OK) return rc;
     h = ho; w = wo;
   }
@@ -1519,6 +1640,7 @@ static int effnet_forward16(const spr_effnet_plan* plan, const uint8_t* images, 
         rc = launch_gemm16_raw<3, 1>(kind, o.cin_p, o.cout_p, o.act, w16, pk + o.b_off, cur, n, h, w, res, dst, o32, sc, o.cout, s);
       else
         rc = launch_gemm16_raw<1, 1>(kind, o.cin_p, o.cout_p, o.act, w16, pk + o.b_off, cur, n, h, w, res, dst, o32, sc, o.cout, s);
+      if (rc == SPR_OK) rc = trace_copy(trace, &lay, i, last ? static_cast<const void*>(out) : dst, s);
       if (rc != SPR_OK) return rc;
       if (o.stride == 2) { h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
       if (o.block_end) {
@@ -1541,6 +1663,7 @@ static int effnet_forward16(const spr_effnet_plan* plan, const uint8_t* images, 
         hipLaunchKernelGGL(enet_dw16_kernel<SPR_BF16>, grid, dim3(kThreads), 0, s, cur, static_cast<int>(n), h, w, o.cin_p, o.stride,
                            o.ks, pk + o.w_off, pk + o.b_off, dst);
       rc = check_launch("enet_dw16_kernel");
+      if (rc == SPR_OK) rc = trace_copy(trace, &lay, i, dst, s);
       if (rc != SPR_OK) return rc;
       h = ho; w = wo;
       cur = dst;
@@ -1554,11 +1677,29 @@ static int effnet_forward16(const spr_effnet_plan* plan, const uint8_t* images, 
       rc = check_launch("enet_pool16_kernel");
       if (rc != SPR_OK) return rc;
       rc = launch_enet_fc(pooled, n, o.cin_p, o.sq, pk + o.w_off, pk + o.b_off, pk + o.w2_off, pk + o.b2_off, hidden, factors, s);
+      if (rc == SPR_OK) rc = trace_copy(trace, &lay, i, factors, s);
       if (rc != SPR_OK) return rc;
       scale = factors;
     }
   }
   return SPR_OK;
+}
+
+extern "C" int spr_effnet_forward_trace(spr_effnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                                        int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
+                                        void* workspace, float* out, void* trace, spr_stream_t stream) {
+  if (!plan || !trace) { set_error("spr_effnet_forward_trace: null pointer"); return SPR_ERR_ARG; }
+  if (plan->compute == SPR_F32) { set_error("spr_effnet_forward_trace: 16-bit plans only"); return SPR_ERR_UNSUPPORTED; }
+  if (n < 0 || n > 65535 || in_h < 32 || in_w < 32 || (in_channels != 1 && in_channels != 3)) {
+    set_error("spr_effnet_forward_trace: bad sizes (n in [0, 65535], images at least 32 x 32, in_channels 1 or 3)");
+    return SPR_ERR_ARG;
+  }
+  if (n == 0) return SPR_OK;
+  if (!images || !mean3 || !inv_std3 || !packed || !out || !workspace) { set_error("spr_effnet_forward_trace: null pointer"); return SPR_ERR_ARG; }
+  const size_t buf_bytes = align_up(effnet_buf_floats(plan, n, in_h, in_w) * sizeof(float), 256);
+  return effnet_forward16(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, static_cast<const float*>(packed),
+                          static_cast<unsigned char*>(workspace), buf_bytes, out, static_cast<hipStream_t>(stream),
+                          static_cast<unsigned char*>(trace));
 }
 
 extern "C" int spr_effnet_forward(spr_effnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
@@ -1576,7 +1717,7 @@ extern "C" int spr_effnet_forward(spr_effnet_plan* plan, const uint8_t* images, 
   const size_t buf_bytes = align_up(effnet_buf_floats(plan, n, in_h, in_w) * sizeof(float), 256);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   if (plan->compute != SPR_F32)
-    return effnet_forward16(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, pk, ws, buf_bytes, out, s);
+    return effnet_forward16(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, pk, ws, buf_bytes, out, s, nullptr);
   float* x = reinterpret_cast<float*>(ws);                    // block input
   float* t1 = reinterpret_cast<float*>(ws + buf_bytes);
   float* t2 = reinterpret_cast<float*>(ws + 2 * buf_bytes);
