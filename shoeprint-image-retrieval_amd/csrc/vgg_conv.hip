@@ -22,7 +22,7 @@
 #include <new>
 #include <vector>
 
-#include "spr_common.h"
+#include "conv_gemm.h"
 
 namespace spr {
 namespace {
@@ -514,7 +514,7 @@ static_assert(kConvLds == kConvLdsBytes, "one LDS size");
 }  // namespace
 
 // The 16-bit 3x3 / stride 1 convolution for other plans of the library (the ResNet's bottleneck 3x3 layers: the input patch
-// staged once serves all nine taps, 164 flop per staged byte against 43 of the tap-by-tap GEMM tiles of resnet.hip).
+// staged once serves all nine taps, 164 flop per staged byte against 43 of the tap-by-tap GEMM tiles of conv_gemm.hip).
 // in / out: NHWC 16-bit; weights as pack_conv16_3x3 writes them.
 int pack_conv16_3x3(int kind, const float* w, const float* b, float* packed, size_t w_off, size_t b_off, int cin, int cout,
                     hipStream_t s) {
@@ -682,7 +682,7 @@ extern "C" int spr_vgg16_pack_weights(spr_vgg16_plan* plan, const float* const* 
     hipStream_t hs = static_cast<hipStream_t>(stream);
     if (i == 0 && plan->compute != SPR_F32 && plan->stages.size() > 1) {
       // 16-bit plans: the first convolution runs on the matrix cores too (K = 27 padded to 32), unless it is the whole plan
-      const int rc0 = pack_first16(plan->compute, weights[i], biases[i], static_cast<float*>(packed), s.w_off, s.b_off, hs);
+      const int rc0 = pack_stem16(plan->compute, 3, weights[i], biases[i], static_cast<float*>(packed), s.w_off, s.b_off, hs);
       if (rc0 != SPR_OK) return rc0;
       continue;
     }
@@ -764,9 +764,9 @@ static int vgg_forward(spr_vgg16_plan* plan, const uint8_t* images, int64_t n, i
       if (tap_convs[t] == static_cast<int>(i)) tap = tap_out[t];
     const unsigned tiles = static_cast<unsigned>(ceil_div(h, kTile) * ceil_div(w, kTile));
     if (i == 0 && plan->compute != SPR_F32 && !last) {
-      const int rc = launch_first16(plan->compute, images, n, h, w, in_channels, mean3, inv_std3,
-                                    reinterpret_cast<const uint16_t*>(pk + st.w_off), pk + st.b_off, st.relu,
-                                    reinterpret_cast<uint16_t*>(dst), s);
+      const int rc = launch_stem16(plan->compute, 3, 1, images, n, h, w, in_channels, mean3, inv_std3,
+                                   reinterpret_cast<const uint16_t*>(pk + st.w_off), pk + st.b_off, st.relu,
+                                   reinterpret_cast<uint16_t*>(dst), s);
       if (rc != SPR_OK) return rc;
     } else if (i == 0) {
       hipLaunchKernelGGL(conv_first_kernel, dim3(tiles, static_cast<unsigned>(n)), dim3(kThreads), 0, s, images, h, w,

@@ -6,9 +6,9 @@ Drop-in for ``src/shoeprint_image_retrieval/network.py``:
 * ``Model.get_feature_maps(img) -> float32 [C, h, w]``            (network.py:210-244)
 * ``Model.get_multiple_feature_maps(images, *, progress=True)``   (network.py:246-269)
 
-``block`` is the slice end into ``vgg16().features`` (network.py:185).  The forward pass is the HIP
-library's ``spr_vgg16_forward`` (implicit-GEMM 3x3 convolutions on the fp32 matrix cores with bias /
-ReLU / max-pool fused, pre-processing fused into the first layer) and — unlike the reference's one
+``block`` is the slice end into the backbone's ``features`` (network.py:185).  The forward pass is the HIP
+library's ``spr_<family>_forward`` (for the plain VGGs: implicit-GEMM 3x3 convolutions on the fp32 matrix cores with
+bias / ReLU / max-pool fused, pre-processing fused into the first layer) and — unlike the reference's one
 image per launch (network.py:228) — runs whole batches; ``extract_device`` keeps the features in HBM
 for the scorer.  Unknown ``model.type`` raises ``LookupError("Model string not found")`` as the
 reference does (network.py:180-182).  ``EfficientNetV2_S / _M / _L`` (network.py:163-175; run.toml's default) and
@@ -45,7 +45,6 @@ _VGG_MODELS = {"VGG16": (0, VGG16_MEAN, VGG16_STD), "VGG19": (1, IMAGENET_MEAN, 
 # BUILD-DEFINED (BASELINE.json config 3; the reference has no ResNet branch): torchvision's resnet50 cut after `block` of its
 # top-level children [conv1, bn1, relu, maxpool, layer1, layer2, layer3] - block 5 / 6 / 7 - with the default transforms
 _RESNET_MODELS = {"ResNet50": (IMAGENET_MEAN, IMAGENET_STD)}
-# network.py:163-175: arch id of spr_effnet_plan_create, mean, std (EfficientNetV2_L was trained on 0.5 / 0.5)
 # network.py:139-175: arch id of spr_effnet_plan_create, mean, std (EfficientNetV2_L was trained on 0.5 / 0.5), BatchNorm eps
 # (torchvision builds efficientnet_v2_* and efficientnet_b5 / b6 / b7 with eps = 1e-3, the others with the default 1e-5)
 _EFFNET_MODELS = {"EfficientNetV2_S": (0, IMAGENET_MEAN, IMAGENET_STD, 1e-3), "EfficientNetV2_M": (1, IMAGENET_MEAN, IMAGENET_STD, 1e-3),
@@ -53,9 +52,6 @@ _EFFNET_MODELS = {"EfficientNetV2_S": (0, IMAGENET_MEAN, IMAGENET_STD, 1e-3), "E
                   "EfficientNet_B1": (3, IMAGENET_MEAN, IMAGENET_STD, 1e-5), "EfficientNet_B2": (4, IMAGENET_MEAN, IMAGENET_STD, 1e-5),
                   "EfficientNet_B3": (5, IMAGENET_MEAN, IMAGENET_STD, 1e-5), "EfficientNet_B4": (6, IMAGENET_MEAN, IMAGENET_STD, 1e-5),
                   "EfficientNet_B5": (7, IMAGENET_MEAN, IMAGENET_STD, 1e-3), "EfficientNet_B7": (8, IMAGENET_MEAN, IMAGENET_STD, 1e-3)}
-_REFERENCE_MODELS = {"EfficientNet_B1", "EfficientNet_B2", "EfficientNet_B3", "EfficientNet_B4",
-                     "EfficientNet_B5", "EfficientNet_B7", "EfficientNetV2_S", "EfficientNetV2_M", "EfficientNetV2_L",
-                     "DenseNet_201"}
 _COMPUTE = {"float32": _lib.F32, "float16": _lib.F16, "bfloat16": _lib.BF16}
 _warned = False
 
@@ -86,27 +82,25 @@ def effnet_state_names(ops) -> list[tuple[str, str]]:
     return names
 
 
-def effnet_plan_ops(lib, handle) -> list[dict]:
-    """The op list of an spr_effnet_plan (see Model.effnet_ops)."""
-    keys = ("kind", "cin", "cout", "cin_p", "cout_p", "ks", "stride", "act", "res", "sq", "feature", "w_off", "b_off",
-            "w2_off", "b2_off", "block_end")
+def _plan_ops(lib, handle, prefix: str, width: int, keys) -> list[dict]:
     out = []
-    for i in range(lib.spr_effnet_num_ops(handle)):
-        info = (C.c_int32 * 16)()
-        lib.check(lib.spr_effnet_op_info(handle, i, info))
+    for i in range(getattr(lib, f"spr_{prefix}_num_ops")(handle)):
+        info = (C.c_int32 * width)()
+        lib.check(getattr(lib, f"spr_{prefix}_op_info")(handle, i, info))
         out.append(dict(zip(keys, list(info))))
     return out
+
+
+def effnet_plan_ops(lib, handle) -> list[dict]:
+    """The op list of an spr_effnet_plan (see Model.effnet_ops)."""
+    return _plan_ops(lib, handle, "effnet", 16, ("kind", "cin", "cout", "cin_p", "cout_p", "ks", "stride", "act", "res", "sq",
+                                                 "feature", "w_off", "b_off", "w2_off", "b2_off", "block_end"))
 
 
 def densenet_plan_ops(lib, handle) -> list[dict]:
     """The op list of an spr_densenet_plan (see Model.densenet_ops)."""
-    keys = ("kind", "cin", "cout", "c_off", "ctot", "flags", "feature", "w_off", "b_off", "s_off", "t_off")
-    out = []
-    for i in range(lib.spr_densenet_num_ops(handle)):
-        info = (C.c_int32 * 12)()
-        lib.check(lib.spr_densenet_op_info(handle, i, info))
-        out.append(dict(zip(keys, list(info))))
-    return out
+    return _plan_ops(lib, handle, "densenet", 12, ("kind", "cin", "cout", "c_off", "ctot", "flags", "feature", "w_off", "b_off",
+                                                   "s_off", "t_off"))
 
 
 def densenet_state_names(ops) -> list[tuple]:
@@ -133,126 +127,173 @@ def densenet_state_names(ops) -> list[tuple]:
     return names
 
 
-class Model:
-    """Operate on the truncated VGG16 and its pre-processing (reference network.py:90-269)."""
+# ---------------------------------------------------------------------- parameters: reading, folding, layouts
+_BN_FIELDS = ("weight", "bias", "running_mean", "running_var")
 
-    def __init__(self, config: dict, block: int, *, device=None, library: _lib.Library | None = None,
-                 parameters: list[tuple[np.ndarray, np.ndarray]] | None = None, batch_size: int = 16):
-        self.config = config
-        model_cfg = config["model"]
-        self.clahe_clip_limit = float(model_cfg.get("clahe_clip_limit", 2.0))
-        self.clahe_tile_grid_size = tuple(model_cfg.get("clahe_tile_grid_size", (8, 8)))
-        model_str = model_cfg["type"]
-        self.resnet = model_str in _RESNET_MODELS
-        self.effnet = model_str in _EFFNET_MODELS
-        self.densenet = model_str == "DenseNet_201"
-        if model_str not in _VGG_MODELS and not self.resnet and not self.effnet and not self.densenet:
-            if model_str in _REFERENCE_MODELS:
-                raise NotImplementedError(f"backbone {model_str} is not built on MI355X yet (SURVEY §8 f4); "
-                                          f"use one of {sorted(_VGG_MODELS) + sorted(_EFFNET_MODELS)}")
-            raise LookupError("Model string not found")  # network.py:180-182
-        self.model_str = model_str
-        if self.resnet:
-            self.arch, (self.mean, self.std) = -1, _RESNET_MODELS[model_str]
-        elif self.effnet:
-            self.arch, self.mean, self.std, self.bn_eps = _EFFNET_MODELS[model_str]
-        elif self.densenet:
-            self.arch, self.mean, self.std, self.bn_eps = -2, IMAGENET_MEAN, IMAGENET_STD, 1e-5
-        else:
-            self.arch, self.mean, self.std = _VGG_MODELS[model_str]
-        self.block = int(block)
-        self.batch_size = int(batch_size)
-        self.lib = library or _lib.load_library()
-        if device is None:
-            from .device import TorchDevice
 
-            device = TorchDevice()
-        self.dev = device
-        # [mi355x].extractor_dtype: compute type of the convolutions behind the first layer ("float32": the f32 matrix cores,
-        # exact, the reference's arithmetic; "bfloat16" / "float16": 16-bit operands, f32 accumulation - BASELINE configs 3 / 5)
-        self.compute = str((config.get("mi355x") or {}).get("extractor_dtype", "float32") or "float32")
-        if self.compute not in _COMPUTE:
-            raise ValueError(f"[mi355x].extractor_dtype = {self.compute!r}: expected one of {sorted(_COMPUTE)}")
-        if self.compute != "float32" and self.densenet:
-            raise NotImplementedError(f"{model_str}: the 16-bit matrix-core path is built for the VGG, ResNet50 and EfficientNet "
-                                      "extractors; use [mi355x].extractor_dtype = \"float32\"")
-        handle = C.c_void_p()
-        if self.densenet:
-            self.lib.check(self.lib.spr_densenet_plan_create(self.block, C.byref(handle)))
-            self.handle = handle
-            self.n_convs = self.lib.spr_densenet_num_ops(handle)
-            if parameters is None:
-                parameters = self._load_densenet_parameters(config)
-            self._set_densenet_parameters(parameters)
-            return
-        if self.effnet:
-            self.lib.check(self.lib.spr_effnet_plan_create_ex(self.arch, self.block, _COMPUTE[self.compute], C.byref(handle)))
-            self.handle = handle
-            self.n_convs = self.lib.spr_effnet_num_ops(handle)
-            if parameters is None:
-                parameters = self._load_effnet_parameters(config)
-            self._set_effnet_parameters(parameters)
-            return
-        if self.resnet:
-            self.lib.check(self.lib.spr_resnet_plan_create_ex(self.block, _COMPUTE[self.compute], C.byref(handle)))
-            self.handle = handle
-            self.n_convs = self.lib.spr_resnet_num_convs(handle)
-            if parameters is None:
-                parameters = self._load_resnet_parameters(config)
-            self._set_resnet_parameters(parameters)
-            return
-        self.lib.check(self.lib.spr_vgg_plan_create_ex(self.arch, self.block, _COMPUTE[self.compute], C.byref(handle)))
-        self.handle = handle
-        self.n_convs = self.lib.spr_vgg16_num_convs(handle)
-        if parameters is None:
-            parameters = self._load_parameters(config)
-        self._set_parameters(parameters)
+def _state(state, module: str, *fields) -> tuple:
+    return tuple(state[f"{module}.{n}"].float().numpy() for n in fields)
 
-    # ------------------------------------------------------------------ EfficientNet B1 .. B7 and V2 (network.py:139-175)
-    def effnet_ops(self) -> list[dict]:
-        """The flattened layers of features[:block]: kind (0 convolution, 1 depthwise 3x3, 2 squeeze-excitation), real and
-        padded widths, kernel size, stride, activation, residual flag, hidden width, index into ``features`` and the offsets
-        (floats) of the layer's parameters in the packed buffer."""
-        return effnet_plan_ops(self.lib, self.handle)
 
-    def _load_effnet_parameters(self, config):
-        global _warned
-        path = config.get("mi355x", {}).get("weights", "")
-        ops = self.effnet_ops()
-        if path:
-            import torch
+def _conv_state(state, conv: str, bn: str | None = None) -> tuple:
+    """(weight, bias[, gamma, beta, running mean, running variance]) of a convolution (zero bias where the module has
+    none) and the BatchNorm2d behind it."""
+    w, = _state(state, conv, "weight")
+    b = _state(state, conv, "bias")[0] if f"{conv}.bias" in state else np.zeros(w.shape[0], np.float32)
+    return (w, b) + (_state(state, bn, *_BN_FIELDS) if bn else ())
 
-            state = torch.load(path, map_location="cpu", weights_only=True)
-            params = []
-            for op, names in zip(ops, effnet_state_names(ops)):
-                if op["kind"] == 2:
-                    fc1, fc2 = names
-                    params.append(tuple(state[f"{m}.{n}"].float().numpy() for m in (fc1, fc2) for n in ("weight", "bias")))
-                else:
-                    conv, bn = names
-                    w = state[f"{conv}.weight"].float().numpy()
-                    params.append((w, np.zeros(w.shape[0], np.float32)) + tuple(
-                        state[f"{bn}.{n}"].float().numpy() for n in ("weight", "bias", "running_mean", "running_var")))
-            return params
-        if not _warned:
-            print(f"shoeprint_image_retrieval_amd: no [mi355x].weights given — using seeded synthetic {self.model_str} "
-                  "weights (pretrained ImageNet weights cannot be downloaded offline)", file=sys.stderr)
-            _warned = True
-        return synth.effnet_parameters(1234, ops)
 
-    def _set_effnet_parameters(self, parameters):
-        ops = self.effnet_ops()
-        if len(parameters) < len(ops):
-            raise ValueError(f"{len(ops)} layers need parameters, got {len(parameters)}")
-        packed = np.zeros(self.lib.spr_effnet_packed_bytes(self.handle) // 4, np.float32)
+def _fold_bn(w, b, gamma, beta, mu, var, eps):
+    """Eval-mode BatchNorm2d behind a convolution is y = (x - mean) * gamma / sqrt(var + eps) + beta: folded into the
+    convolution's (w, b) (float32, as the layer itself computes)."""
+    scale = gamma / np.sqrt(var + np.float32(eps))
+    return w * scale[:, None, None, None], (b - mu) * scale + beta
+
+
+def _gemm_layout(w, cout_p: int, cin_p: int, kc: int) -> np.ndarray:
+    """[cout][cin][k][k] -> [cout_p / 64][K / kc][64][kc], zero-padded, K index = tap * cin_p + c: kc = 16 is
+    conv_gemm_kernel's layout, kc = 64 conv_gemm16_kernel's."""
+    cout, cin, k, _ = w.shape
+    wp = np.zeros((cout_p, k * k, cin_p), np.float32)
+    wp[:cout, :, :cin] = w.reshape(cout, cin, k * k).transpose(0, 2, 1)
+    return np.ascontiguousarray(wp.reshape(cout_p // 64, 64, k * k * cin_p // kc, kc).transpose(0, 2, 1, 3)).ravel()
+
+
+def _padded(a, n: int) -> np.ndarray:
+    out = np.zeros(n, np.float32)
+    out[:a.size] = a
+    return out
+
+
+# ---------------------------------------------------------------------- backbone families
+class _Family:
+    """What ``Model`` needs to know about one backbone family: its C entry points (``spr_<prefix>_*``), whether it has a
+    16-bit path, how its layers are listed, named in a torchvision state dict, read from one, seeded and packed."""
+    prefix = count = ""  # spr_<prefix>_<count>: the number of layers
+    lister = ""          # the Model method that lists the layers
+    seeder = None        # synth.*_parameters(seed, layers)
+    half = True          # float16 / bfloat16 plans exist
+    custom_op = False    # also served by the registered torch custom op (keyed by arch)
+
+    def __init__(self, arch, mean, std, bn_eps=BN_EPS):
+        self.arch, self.mean, self.std, self.bn_eps = arch, mean, std, bn_eps
+
+    def fn(self, lib, name):
+        return getattr(lib, f"spr_{self.prefix}_{name}")
+
+    def layers(self, m):
+        return getattr(m, self.lister)()
+
+    def read(self, state, layer, names):
+        """One layer's parameters out of a torchvision state dict, given its module names."""
+        return _conv_state(state, *names)
+
+    def seeded(self, layers):
+        return type(self).seeder(1234, layers)
+
+    def pack_on_device(self, m, folded):
+        """Upload every layer's (w, b) and let the library's packer lay them out (VGG, ResNet)."""
+        dev = m.dev
+        m._w_dev, m._b_dev = [], []
+        for w, b in folded:
+            m._w_dev.append(dev.to_device(np.ascontiguousarray(w)))
+            m._b_dev.append(dev.to_device(np.ascontiguousarray(b)))
+        n = len(folded)
+        wp = (C.c_void_p * n)(*[dev.ptr(t) for t in m._w_dev])
+        bp = (C.c_void_p * n)(*[dev.ptr(t) for t in m._b_dev])
+        m.packed = dev.empty_bytes(max(16, self.fn(m.lib, "packed_bytes")(m.handle)))
+        m.lib.check(self.fn(m.lib, "pack_weights")(m.handle, wp, bp, dev.ptr(m.packed), dev.stream()))
+        dev.synchronize()
+
+
+class _Vgg(_Family):
+    """Layers: (cin, cout, index in model.features, BatchNorm2d inside the truncation)."""
+    prefix, count, custom_op = "vgg16", "num_convs", True
+
+    def create(self, m, handle):
+        return m.lib.spr_vgg_plan_create_ex(self.arch, m.block, _COMPUTE[m.compute], handle)
+
+    def layers(self, m):
+        return [shape + info for shape, info in zip(m.conv_shapes(), m.conv_info())]
+
+    def names(self, m, layers):  # BatchNorm2d at features.<k + 1>
+        return [(f"features.{k}", f"features.{k + 1}" if bn else None) for _, _, k, bn in layers]
+
+    def seeded(self, layers):
+        return synth.vgg_parameters(1234, [l[:2] for l in layers], [l[3] for l in layers])
+
+    def pack(self, m, layers, parameters):
+        folded = []
+        for (cin, cout, _, bn), p in zip(layers, parameters):
+            w, b = (np.ascontiguousarray(t, dtype=np.float32) for t in p[:2])
+            if bn:
+                if len(p) != 6:
+                    raise ValueError("a convolution followed by BatchNorm2d needs (w, b, gamma, beta, mean, var)")
+                w, b = _fold_bn(w, b, *(np.asarray(t, dtype=np.float32) for t in p[2:]), self.bn_eps)
+            if w.shape != (cout, cin, 3, 3) or b.shape != (cout,):
+                raise ValueError(f"parameter shape {w.shape}/{b.shape} does not match conv {cin}->{cout}")
+            folded.append((w, b))
+        self.pack_on_device(m, folded)
+
+
+class _ResNet(_Family):
+    """Layers: ``Model.conv_specs`` - (cin, cout, ksize, stride, role)."""
+    prefix, count, lister, seeder = "resnet", "num_convs", "conv_specs", synth.resnet_parameters
+
+    def create(self, m, handle):
+        return m.lib.spr_resnet_plan_create_ex(m.block, _COMPUTE[m.compute], handle)
+
+    def names(self, m, layers):
+        """(convolution, BatchNorm) module names in a torchvision resnet50 state dict, in conv_specs order."""
+        names = [("conv1", "bn1")]
+        for layer in range(m.block - 4):
+            for b in range((3, 4, 6)[layer]):
+                pre = f"layer{layer + 1}.{b}"
+                names += [(f"{pre}.conv1", f"{pre}.bn1"), (f"{pre}.conv2", f"{pre}.bn2"), (f"{pre}.conv3", f"{pre}.bn3")]
+                if b == 0:
+                    names.append((f"{pre}.downsample.0", f"{pre}.downsample.1"))
+        return names
+
+    def pack(self, m, layers, parameters):
+        folded = []
+        for (cin, cout, ks, _stride, _role), p in zip(layers, parameters):
+            if len(p) != 6:
+                raise ValueError("every ResNet convolution needs (w, b, gamma, beta, running_mean, running_var)")
+            w, b, *bn = (np.asarray(t, dtype=np.float32) for t in p)
+            if w.shape != (cout, cin, ks, ks) or b.shape != (cout,):
+                raise ValueError(f"parameter shape {w.shape}/{b.shape} does not match conv {cin}->{cout} {ks}x{ks}")
+            folded.append(_fold_bn(w, b, *bn, self.bn_eps))
+        self.pack_on_device(m, folded)
+
+
+class _EffNet(_Family):
+    """Layers: ``Model.effnet_ops``.  BatchNorm folded and parameters packed here, in numpy."""
+    prefix, count, lister, seeder = "effnet", "num_ops", "effnet_ops", synth.effnet_parameters
+
+    def create(self, m, handle):
+        return m.lib.spr_effnet_plan_create_ex(self.arch, m.block, _COMPUTE[m.compute], handle)
+
+    def names(self, m, layers):
+        return effnet_state_names(layers)
+
+    def read(self, state, op, names):
+        if op["kind"] == 2:
+            return _state(state, names[0], "weight", "bias") + _state(state, names[1], "weight", "bias")
+        return _conv_state(state, *names)
+
+    def pack(self, m, ops, parameters):
+        packed = np.zeros(m.lib.spr_effnet_packed_bytes(m.handle) // 4, np.float32)
         packed16 = packed.view(np.uint16)  # 16-bit plans: the convolutions' weights as float16 / bfloat16 bit patterns
-        half = self.compute != "float32"
+        half = m.compute != "float32"
         if half and len(ops) < 2:
             raise NotImplementedError("a 16-bit EfficientNet plan needs layers behind the stem (block >= 2)")
 
         def bits16(a):
             a = np.ascontiguousarray(a, dtype=np.float32)
-            return synth.bfloat16_bits(a) if self.compute == "bfloat16" else a.astype(np.float16).view(np.uint16)
+            return synth.bfloat16_bits(a) if m.compute == "bfloat16" else a.astype(np.float16).view(np.uint16)
+
+        def put(off, a):
+            packed[off:off + a.size] = a.ravel()
 
         for k_op, (op, p) in enumerate(zip(ops, parameters)):
             p = [np.asarray(t, dtype=np.float32) for t in p]
@@ -263,105 +304,62 @@ class Model:
                     raise ValueError(f"squeeze-excitation of width {c}: parameters do not match (hidden width {sq})")
                 a = np.zeros((sq, cp), np.float32); a[:, :c] = w1.reshape(sq, c)
                 b = np.zeros((cp, sq), np.float32); b[:c] = w2.reshape(c, sq)
-                bb = np.zeros(cp, np.float32); bb[:c] = b2
-                packed[op["w_off"]:op["w_off"] + a.size] = a.ravel()
-                packed[op["b_off"]:op["b_off"] + sq] = b1
-                packed[op["w2_off"]:op["w2_off"] + b.size] = b.ravel()
-                packed[op["b2_off"]:op["b2_off"] + cp] = bb
+                put(op["w_off"], a); put(op["b_off"], b1); put(op["w2_off"], b); put(op["b2_off"], _padded(b2, cp))
                 continue
             w, b, gamma, beta, mu, var = p
-            scale = gamma / np.sqrt(var + np.float32(self.bn_eps))  # eval-mode BatchNorm folded into the convolution
-            w = w * scale[:, None, None, None]
-            b = (b - mu) * scale + beta
+            w, b = _fold_bn(w, b, gamma, beta, mu, var, self.bn_eps)
             ks, cin, cout, cin_p, cout_p = op["ks"], op["cin"], op["cout"], op["cin_p"], op["cout_p"]
             if op["kind"] == 1:
                 if w.shape != (cin, 1, ks, ks):
                     raise ValueError(f"depthwise parameter shape {w.shape} does not match width {cin}, kernel {ks}")
                 a = np.zeros((ks * ks, cin_p), np.float32); a[:, :cin] = w.reshape(cin, ks * ks).T
-                bb = np.zeros(cin_p, np.float32); bb[:cin] = b
-                packed[op["w_off"]:op["w_off"] + a.size] = a.ravel()
-                packed[op["b_off"]:op["b_off"] + cin_p] = bb
+                put(op["w_off"], a); put(op["b_off"], _padded(b, cin_p))
                 continue
             if w.shape != (cout, cin, ks, ks):
                 raise ValueError(f"parameter shape {w.shape} does not match conv {cin}->{cout} {ks}x{ks}")
-            bb = np.zeros(cout_p, np.float32); bb[:cout] = b
+            put(op["b_off"], _padded(b, cout_p))
             if half and k_op == 0:
                 # the stem of a 16-bit plan: [k / 8][64][8], k = tap * 3 + plane, 27 real values of 32 (stem16_kernel)
                 ws = np.zeros((32, 64), np.float32)
                 ws[:27, :cout] = w.transpose(2, 3, 1, 0).reshape(27, cout)  # [ky][kx][c][n] -> k = (ky * 3 + kx) * 3 + c
                 ws = ws.reshape(4, 8, 64).transpose(0, 2, 1)               # [k / 8][n][k % 8]
                 packed16[2 * op["w_off"]:2 * op["w_off"] + ws.size] = bits16(ws).ravel()
-                packed[op["b_off"]:op["b_off"] + cout_p] = bb
-                continue
-            if half:
-                # [cout_p / 64][K / 64][64][64] with K index = tap * cin_p + c (conv_gemm16_kernel)
-                wk = np.zeros((cout_p, ks * ks, cin_p), np.float32)
-                wk[:cout, :, :cin] = w.reshape(cout, cin, ks * ks).transpose(0, 2, 1)
-                kk = ks * ks * cin_p
-                wk = wk.reshape(cout_p // 64, 64, kk // 64, 64).transpose(0, 2, 1, 3)
-                packed16[2 * op["w_off"]:2 * op["w_off"] + wk.size] = bits16(wk).ravel()
-                packed[op["b_off"]:op["b_off"] + cout_p] = bb
-                continue
-            wp = np.zeros((cout_p, ks * ks, cin_p), np.float32)
-            wp[:cout, :, :cin] = w.reshape(cout, cin, ks * ks).transpose(0, 2, 1)  # K index = tap * cin_p + c
-            k = ks * ks * cin_p
-            wp = wp.reshape(cout_p // 64, 64, k // 16, 16).transpose(0, 2, 1, 3)  # [cout/64][K/16][64][16]
-            bb = np.zeros(cout_p, np.float32); bb[:cout] = b
-            packed[op["w_off"]:op["w_off"] + wp.size] = np.ascontiguousarray(wp).ravel()
-            packed[op["b_off"]:op["b_off"] + cout_p] = bb
-        self.packed = self.dev.to_device(packed)
+            elif half:
+                wk = _gemm_layout(w, cout_p, cin_p, 64)
+                packed16[2 * op["w_off"]:2 * op["w_off"] + wk.size] = bits16(wk)
+            else:
+                put(op["w_off"], _gemm_layout(w, cout_p, cin_p, 16))
+        m.packed = m.dev.to_device(packed)
 
-    # ------------------------------------------------------------------ DenseNet_201 (network.py:176-179)
-    def densenet_ops(self) -> list[dict]:
-        """The layers of features[:block]: kind (0 stem, 1 dense 1x1, 2 dense 3x3, 3 transition, 4 closing BatchNorm), widths,
-        channel offset / width of the block tensor, stem flags, index into ``features`` and packed offsets (floats)."""
-        return densenet_plan_ops(self.lib, self.handle)
 
-    def _load_densenet_parameters(self, config):
-        global _warned
-        path = config.get("mi355x", {}).get("weights", "")
-        ops = self.densenet_ops()
-        if path:
-            import torch
+class _DenseNet(_Family):
+    """Layers: ``Model.densenet_ops``; parameters per layer in torchvision's module order (synth.densenet_parameters)."""
+    prefix, count, lister, seeder, half = "densenet", "num_ops", "densenet_ops", synth.densenet_parameters, False
 
-            state = torch.load(path, map_location="cpu", weights_only=True)
-            bn = lambda m: tuple(state[f"{m}.{n}"].float().numpy() for n in ("weight", "bias", "running_mean", "running_var"))
-            wt = lambda m: state[f"{m}.weight"].float().numpy()
-            params = []
-            for op, names in zip(ops, densenet_state_names(ops)):
-                if op["kind"] == 0:
-                    params.append((wt(names[0]),) + bn(names[1]))
-                elif op["kind"] == 1:
-                    params.append(bn(names[0]) + (wt(names[1]),) + bn(names[2]))
-                elif op["kind"] == 2:
-                    params.append((wt(names[0]),))
-                elif op["kind"] == 3:
-                    params.append(bn(names[0]) + (wt(names[1]),))
-                else:
-                    params.append(bn(names[0]))
-            return params
-        if not _warned:
-            print(f"shoeprint_image_retrieval_amd: no [mi355x].weights given — using seeded synthetic {self.model_str} "
-                  "weights (pretrained ImageNet weights cannot be downloaded offline)", file=sys.stderr)
-            _warned = True
-        return synth.densenet_parameters(1234, ops)
+    def create(self, m, handle):
+        return m.lib.spr_densenet_plan_create(m.block, handle)
 
-    def _set_densenet_parameters(self, parameters):
-        ops = self.densenet_ops()
-        if len(parameters) < len(ops):
-            raise ValueError(f"{len(ops)} layers need parameters, got {len(parameters)}")
+    def names(self, m, layers):
+        return densenet_state_names(layers)
+
+    def read(self, state, op, names):
+        bn = lambda k: _state(state, names[k], *_BN_FIELDS)
+        wt = lambda k: _state(state, names[k], "weight")
+        if op["kind"] == 0:
+            return wt(0) + bn(1)
+        if op["kind"] == 1:
+            return bn(0) + wt(1) + bn(2)
+        if op["kind"] == 2:
+            return wt(0)
+        return bn(0) + wt(1) if op["kind"] == 3 else bn(0)
+
+    def pack(self, m, ops, parameters):
         eps = np.float32(self.bn_eps)
-        packed = np.zeros(self.lib.spr_densenet_packed_bytes(self.handle) // 4, np.float32)
+        packed = np.zeros(m.lib.spr_densenet_packed_bytes(m.handle) // 4, np.float32)
 
-        def affine(gamma, beta, mu, var):  # eval-mode BatchNorm as x * s + t
+        def affine(gamma, beta, mu, var):  # eval-mode BatchNorm as x * s + t (in FRONT of a convolution: not folded)
             s = gamma / np.sqrt(var + eps)
             return s, beta - mu * s
-
-        def gemm_pack(w, cout_p):  # [cout][cin][k][k] -> [cout_p/64][K/16][64][16], K index = tap * cin + c
-            cout, cin, k, _ = w.shape
-            wp = np.zeros((cout_p, k * k, cin), np.float32)
-            wp[:cout] = w.reshape(cout, cin, k * k).transpose(0, 2, 1)
-            return np.ascontiguousarray(wp.reshape(cout_p // 64, 64, k * k * cin // 16, 16).transpose(0, 2, 1, 3)).ravel()
 
         def put(off, a):
             a = np.asarray(a, np.float32).ravel()
@@ -385,168 +383,135 @@ class Model:
                 if w.shape != (128, op["cin"], 1, 1):
                     raise ValueError(f"dense 1x1 parameter shape {w.shape} for {op['cin']} input channels")
                 put(op["s_off"], s1); put(op["t_off"], t1)
-                put(op["w_off"], gemm_pack(w * s2[:, None, None, None], 128)); put(op["b_off"], t2)
+                put(op["w_off"], _gemm_layout(w * s2[:, None, None, None], 128, op["cin"], 16)); put(op["b_off"], t2)
             elif op["kind"] == 2:
                 if p[0].shape != (32, 128, 3, 3):
                     raise ValueError(f"dense 3x3 parameter shape {p[0].shape}")
-                put(op["w_off"], gemm_pack(p[0], 64))
+                put(op["w_off"], _gemm_layout(p[0], 64, 128, 16))
             elif op["kind"] == 3:
                 s, t = affine(*p[0:4])
                 if p[4].shape != (op["cout"], op["cin"], 1, 1):
                     raise ValueError(f"transition parameter shape {p[4].shape}")
                 put(op["s_off"], s); put(op["t_off"], t)
-                put(op["w_off"], gemm_pack(p[4], op["cout"]))
+                put(op["w_off"], _gemm_layout(p[4], op["cout"], op["cin"], 16))
             else:
                 s, t = affine(*p[0:4])
                 put(op["s_off"], s); put(op["t_off"], t)
-        self.packed = self.dev.to_device(packed)
+        m.packed = m.dev.to_device(packed)
 
-    # ------------------------------------------------------------------ ResNet50 (build-defined)
-    def conv_specs(self) -> list[tuple[int, int, int, int, int]]:
-        """(cin, cout, ksize, stride, role) of every convolution in torchvision's module order."""
-        out = []
-        for i in range(self.n_convs):
-            v = [C.c_int32() for _ in range(5)]
-            self.lib.check(self.lib.spr_resnet_conv_shape(self.handle, i, *[C.byref(t) for t in v]))
-            out.append(tuple(t.value for t in v))
-        return out
 
-    def _resnet_state_names(self) -> list[tuple[str, str]]:
-        """(convolution, BatchNorm) module names in a torchvision resnet50 state dict, in conv_specs order."""
-        names = [("conv1", "bn1")]
-        for layer in range(self.block - 4):
-            for b in range((3, 4, 6)[layer]):
-                pre = f"layer{layer + 1}.{b}"
-                names += [(f"{pre}.conv1", f"{pre}.bn1"), (f"{pre}.conv2", f"{pre}.bn2"), (f"{pre}.conv3", f"{pre}.bn3")]
-                if b == 0:
-                    names.append((f"{pre}.downsample.0", f"{pre}.downsample.1"))
-        return names
+# model.type -> family.  arch: spr_vgg_arch / the arch id of spr_effnet_plan_create (what the C plans and the torch custom
+# op are keyed by); -1 / -2: ResNet / DenseNet take none
+_FAMILIES: dict[str, _Family] = {
+    **{k: _Vgg(*v) for k, v in _VGG_MODELS.items()},
+    **{k: _ResNet(-1, *v) for k, v in _RESNET_MODELS.items()},
+    **{k: _EffNet(*v) for k, v in _EFFNET_MODELS.items()},
+    "DenseNet_201": _DenseNet(-2, IMAGENET_MEAN, IMAGENET_STD, 1e-5),
+}
 
-    def _load_resnet_parameters(self, config):
+
+class Model:
+    """Operate on one truncated backbone (a ``_Family``) and its pre-processing (reference network.py:90-269)."""
+
+    def __init__(self, config: dict, block: int, *, device=None, library: _lib.Library | None = None,
+                 parameters: list[tuple[np.ndarray, ...]] | None = None, batch_size: int = 16):
+        self.config = config
+        model_cfg = config["model"]
+        self.clahe_clip_limit = float(model_cfg.get("clahe_clip_limit", 2.0))
+        self.clahe_tile_grid_size = tuple(model_cfg.get("clahe_tile_grid_size", (8, 8)))
+        self.model_str = model_cfg["type"]
+        if self.model_str not in _FAMILIES:
+            raise LookupError("Model string not found")  # network.py:180-182
+        fam = self.family = _FAMILIES[self.model_str]
+        self.arch, self.mean, self.std, self.bn_eps = fam.arch, fam.mean, fam.std, fam.bn_eps
+        self.block = int(block)
+        self.batch_size = int(batch_size)
+        self.lib = library or _lib.load_library()
+        if device is None:
+            from .device import TorchDevice
+
+            device = TorchDevice()
+        self.dev = device
+        # [mi355x].extractor_dtype: compute type of the convolutions behind the first layer ("float32": the f32 matrix cores,
+        # exact, the reference's arithmetic; "bfloat16" / "float16": 16-bit operands, f32 accumulation - BASELINE configs 3 / 5)
+        self.compute = str((config.get("mi355x") or {}).get("extractor_dtype", "float32") or "float32")
+        if self.compute not in _COMPUTE:
+            raise ValueError(f"[mi355x].extractor_dtype = {self.compute!r}: expected one of {sorted(_COMPUTE)}")
+        if self.compute != "float32" and not fam.half:
+            raise NotImplementedError(f"{self.model_str}: the 16-bit matrix-core path is built for the VGG, ResNet50 and "
+                                      "EfficientNet extractors; use [mi355x].extractor_dtype = \"float32\"")
+        handle = C.c_void_p()
+        self.lib.check(fam.create(self, C.byref(handle)))
+        self.handle = handle
+        self.n_convs = fam.fn(self.lib, fam.count)(handle)
+        layers = fam.layers(self)
+        if parameters is None:
+            parameters = self._load_parameters(config, layers)
+        if len(parameters) < len(layers):
+            raise ValueError(f"{len(layers)} layers need parameters, got {len(parameters)}")
+        fam.pack(self, layers, parameters)
+
+    resnet = property(lambda self: isinstance(self.family, _ResNet))
+    effnet = property(lambda self: isinstance(self.family, _EffNet))
+    densenet = property(lambda self: isinstance(self.family, _DenseNet))
+
+    def _load_parameters(self, config, layers):
+        """The state dict [mi355x].weights names (torchvision's module names), else seeded stand-ins."""
         global _warned
         path = config.get("mi355x", {}).get("weights", "")
+        fam = self.family
         if path:
             import torch
 
             state = torch.load(path, map_location="cpu", weights_only=True)
-            params = []
-            for conv, bn in self._resnet_state_names():
-                w = state[f"{conv}.weight"].float().numpy()
-                b = state[f"{conv}.bias"].float().numpy() if f"{conv}.bias" in state else np.zeros(w.shape[0], np.float32)
-                params.append((w, b) + tuple(state[f"{bn}.{n}"].float().numpy()
-                                             for n in ("weight", "bias", "running_mean", "running_var")))
-            return params
+            return [fam.read(state, layer, names) for layer, names in zip(layers, fam.names(self, layers))]
         if not _warned:
             print(f"shoeprint_image_retrieval_amd: no [mi355x].weights given — using seeded synthetic {self.model_str} "
                   "weights (pretrained ImageNet weights cannot be downloaded offline)", file=sys.stderr)
             _warned = True
-        return synth.resnet_parameters(1234, self.conv_specs())
+        return fam.seeded(layers)
 
-    def _set_resnet_parameters(self, parameters):
-        specs = self.conv_specs()
-        if len(parameters) < len(specs):
-            raise ValueError(f"{len(specs)} convolutions need parameters, got {len(parameters)}")
-        dev = self.dev
-        self._w_dev, self._b_dev = [], []
-        for (cin, cout, ks, _stride, _role), p in zip(specs, parameters):
-            if len(p) != 6:
-                raise ValueError("every ResNet convolution needs (w, b, gamma, beta, running_mean, running_var)")
-            w, b, gamma, beta, mu, var = (np.asarray(t, dtype=np.float32) for t in p)
-            if w.shape != (cout, cin, ks, ks) or b.shape != (cout,):
-                raise ValueError(f"parameter shape {w.shape}/{b.shape} does not match conv {cin}->{cout} {ks}x{ks}")
-            scale = gamma / np.sqrt(var + np.float32(BN_EPS))  # eval-mode BatchNorm folded into the convolution
-            self._w_dev.append(dev.to_device(np.ascontiguousarray(w * scale[:, None, None, None])))
-            self._b_dev.append(dev.to_device(np.ascontiguousarray((b - mu) * scale + beta)))
-        n = len(specs)
-        wp = (C.c_void_p * n)(*[dev.ptr(t) for t in self._w_dev])
-        bp = (C.c_void_p * n)(*[dev.ptr(t) for t in self._b_dev])
-        self.packed = dev.empty_bytes(max(16, self.lib.spr_resnet_packed_bytes(self.handle)))
-        self.lib.check(self.lib.spr_resnet_pack_weights(self.handle, wp, bp, dev.ptr(self.packed), dev.stream()))
-        dev.synchronize()
+    # ------------------------------------------------------------------ layers
+    def _ints(self, fn, n: int, *args) -> tuple:
+        """The n int32 results of fn(plan, *args, &out_0, ..)."""
+        v = [C.c_int32() for _ in range(n)]
+        self.lib.check(fn(self.handle, *args, *[C.byref(t) for t in v]))
+        return tuple(t.value for t in v)
 
-    # ------------------------------------------------------------------ parameters
     def conv_shapes(self) -> list[tuple[int, int]]:
-        out = []
-        for i in range(self.n_convs):
-            cin, cout = C.c_int32(), C.c_int32()
-            self.lib.check(self.lib.spr_vgg16_conv_shape(self.handle, i, C.byref(cin), C.byref(cout)))
-            out.append((cin.value, cout.value))
-        return out
+        """Plain VGG: (cin, cout) of every convolution."""
+        return [self._ints(self.lib.spr_vgg16_conv_shape, 2, i) for i in range(self.n_convs)]
 
     def conv_info(self) -> list[tuple[int, bool]]:
-        """(index in model.features, BatchNorm2d inside the truncation) of every convolution."""
-        out = []
-        for i in range(self.n_convs):
-            k, bn = C.c_int32(), C.c_int32()
-            self.lib.check(self.lib.spr_vgg_conv_info(self.handle, i, C.byref(k), C.byref(bn)))
-            out.append((k.value, bool(bn.value)))
-        return out
+        """Plain VGG: (index in model.features, BatchNorm2d inside the truncation) of every convolution."""
+        return [(k, bool(bn)) for k, bn in (self._ints(self.lib.spr_vgg_conv_info, 2, i) for i in range(self.n_convs))]
 
-    def _load_parameters(self, config):
-        global _warned
-        path = config.get("mi355x", {}).get("weights", "")
-        if path:
-            import torch
+    def conv_specs(self) -> list[tuple[int, int, int, int, int]]:
+        """ResNet50: (cin, cout, ksize, stride, role) of every convolution in torchvision's module order."""
+        return [self._ints(self.lib.spr_resnet_conv_shape, 5, i) for i in range(self.n_convs)]
 
-            state = torch.load(path, map_location="cpu", weights_only=True)
-            params = []
-            for k, bn in self.conv_info():
-                p = [state[f"features.{k}.weight"].float().numpy(), state[f"features.{k}.bias"].float().numpy()]
-                if bn:  # BatchNorm2d at features.<k+1>: gamma, beta, running mean, running variance
-                    p += [state[f"features.{k + 1}.{n}"].float().numpy()
-                          for n in ("weight", "bias", "running_mean", "running_var")]
-                params.append(tuple(p))
-            return params
-        if not _warned:
-            print(f"shoeprint_image_retrieval_amd: no [mi355x].weights given — using seeded synthetic {self.model_str} "
-                  "weights (pretrained ImageNet weights cannot be downloaded offline)", file=sys.stderr)
-            _warned = True
-        return synth.vgg_parameters(1234, self.conv_shapes(), [bn for _, bn in self.conv_info()])
+    def effnet_ops(self) -> list[dict]:
+        """EfficientNet: the flattened layers of features[:block]: kind (0 convolution, 1 depthwise 3x3, 2 squeeze-excitation),
+        real and padded widths, kernel size, stride, activation, residual flag, hidden width, index into ``features`` and the
+        offsets (floats) of the layer's parameters in the packed buffer."""
+        return effnet_plan_ops(self.lib, self.handle)
 
-    def _set_parameters(self, parameters):
-        shapes = self.conv_shapes()
-        if len(parameters) < len(shapes):
-            raise ValueError(f"{len(shapes)} convolutions need parameters, got {len(parameters)}")
-        dev = self.dev
-        self._w_dev, self._b_dev = [], []
-        for (cin, cout), (_, bn), p in zip(shapes, self.conv_info(), parameters):
-            w = np.ascontiguousarray(p[0], dtype=np.float32)
-            b = np.ascontiguousarray(p[1], dtype=np.float32)
-            if bn:
-                # eval-mode BatchNorm2d after the convolution is y = (x - mean) * gamma / sqrt(var + eps) + beta:
-                # folded into the convolution (float32, as the layer itself computes)
-                if len(p) != 6:
-                    raise ValueError("a convolution followed by BatchNorm2d needs (w, b, gamma, beta, mean, var)")
-                gamma, beta, mu, var = (np.asarray(t, dtype=np.float32) for t in p[2:])
-                scale = gamma / np.sqrt(var + np.float32(BN_EPS))
-                w = np.ascontiguousarray(w * scale[:, None, None, None])
-                b = np.ascontiguousarray((b - mu) * scale + beta)
-            if w.shape != (cout, cin, 3, 3) or b.shape != (cout,):
-                raise ValueError(f"parameter shape {w.shape}/{b.shape} does not match conv {cin}->{cout}")
-            self._w_dev.append(dev.to_device(w))
-            self._b_dev.append(dev.to_device(b))
-        n = len(shapes)
-        wp = (C.c_void_p * n)(*[dev.ptr(t) for t in self._w_dev])
-        bp = (C.c_void_p * n)(*[dev.ptr(t) for t in self._b_dev])
-        self.packed = dev.empty_bytes(max(16, self.lib.spr_vgg16_packed_bytes(self.handle)))
-        self.lib.check(self.lib.spr_vgg16_pack_weights(self.handle, wp, bp, dev.ptr(self.packed), dev.stream()))
-        dev.synchronize()
+    def densenet_ops(self) -> list[dict]:
+        """DenseNet: the layers of features[:block]: kind (0 stem, 1 dense 1x1, 2 dense 3x3, 3 transition, 4 closing BatchNorm),
+        widths, channel offset / width of the block tensor, stem flags, index into ``features`` and packed offsets (floats)."""
+        return densenet_plan_ops(self.lib, self.handle)
 
     # ------------------------------------------------------------------ shapes
     def output_shape(self, in_h: int, in_w: int) -> tuple[int, int, int]:
-        c, h, w = C.c_int32(), C.c_int32(), C.c_int32()
-        fn = (self.lib.spr_densenet_output_shape if self.densenet else self.lib.spr_effnet_output_shape if self.effnet else
-              self.lib.spr_resnet_output_shape if self.resnet else self.lib.spr_vgg16_output_shape)
-        self.lib.check(fn(self.handle, in_h, in_w, C.byref(c), C.byref(h), C.byref(w)))
-        return c.value, h.value, w.value
+        return self._ints(self.family.fn(self.lib, "output_shape"), 3, in_h, in_w)
 
     # ------------------------------------------------------------------ forward
     def extract_device(self, images_dev, in_channels: int = 1):
         """uint8 device batch [N,H,W] (or [N,H,W,3]) -> float32 device features [N,C,h,w] (stays in HBM)."""
-        dev = self.dev
+        dev, fam = self.dev, self.family
         shape = dev.shape(images_dev)
         n, h, w = shape[0], shape[1], shape[2]
-        if self.arch >= 0 and not self.effnet and dev.name == "hip" and self.lib is _lib.load_library():
+        if fam.custom_op and dev.name == "hip" and self.lib is _lib.load_library():
             from . import _torch_ops
 
             if _torch_ops.enabled() and images_dev.is_contiguous() and len(shape) == (4 if in_channels == 3 else 3):
@@ -555,15 +520,11 @@ class Model:
                                                  [float(s) for s in self.std], _COMPUTE[self.compute])
         c, oh, ow = self.output_shape(h, w)
         out = dev.empty((n, c, oh, ow), np.float32)
-        ws_fn = (self.lib.spr_densenet_workspace_bytes if self.densenet else self.lib.spr_effnet_workspace_bytes if self.effnet else
-                 self.lib.spr_resnet_workspace_bytes if self.resnet else self.lib.spr_vgg16_workspace_bytes)
-        fwd = (self.lib.spr_densenet_forward if self.densenet else self.lib.spr_effnet_forward if self.effnet else
-               self.lib.spr_resnet_forward if self.resnet else self.lib.spr_vgg16_forward)
-        ws = dev.empty_bytes(max(16, ws_fn(self.handle, n, h, w)))
+        ws = dev.empty_bytes(max(16, fam.fn(self.lib, "workspace_bytes")(self.handle, n, h, w)))
         mean = (C.c_float * 3)(*self.mean)
         inv_std = (C.c_float * 3)(*[np.float32(1.0) / np.float32(s) for s in self.std])
-        self.lib.check(fwd(self.handle, dev.ptr(images_dev), n, h, w, in_channels, mean, inv_std,
-                                                  dev.ptr(self.packed), dev.ptr(ws), dev.ptr(out), dev.stream()))
+        self.lib.check(fam.fn(self.lib, "forward")(self.handle, dev.ptr(images_dev), n, h, w, in_channels, mean, inv_std,
+                                                   dev.ptr(self.packed), dev.ptr(ws), dev.ptr(out), dev.stream()))
         return out
 
     def extract_taps_device(self, images_dev, tap_features, in_channels: int = 1):
@@ -571,7 +532,7 @@ class Model:
         ``model.features`` like ``block``, each just behind a ReLU (16 = conv3_3, 23 = conv4_3, 30 = conv5_3 for VGG16) -
         as float32 device arrays [N, C_l, h_l, w_l], in that order; a tap equal to ``block`` is the network's output.
         Multi-layer scoring (BASELINE config 5) feeds on this: the reference would run the extractor once per block."""
-        if self.resnet or self.effnet or self.densenet:
+        if not isinstance(self.family, _Vgg):
             raise NotImplementedError("feature taps are built for the plain VGG backbones")
         dev = self.dev
         n, h, w = dev.shape(images_dev)[:3]
@@ -678,9 +639,7 @@ class Model:
 
     def close(self):
         if getattr(self, "handle", None):
-            (self.lib.spr_densenet_plan_destroy if getattr(self, "densenet", False) else
-             self.lib.spr_effnet_plan_destroy if getattr(self, "effnet", False) else
-             self.lib.spr_resnet_plan_destroy if self.resnet else self.lib.spr_vgg16_plan_destroy)(self.handle)
+            self.family.fn(self.lib, "plan_destroy")(self.handle)
             self.handle = None
 
     def __del__(self):  # pragma: no cover
