@@ -3,6 +3,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 #include <new>
 #include <vector>
 
@@ -28,16 +29,19 @@ int check_launch(const char* what) {
   return SPR_OK;
 }
 
+int env_int(const char* name, int fallback) {
+  const char* v = std::getenv(name);
+  return v && *v ? std::atoi(v) : fallback;
+}
+
+bool team_schedule() { return env_int("SPR_NCC_TEAM", 0) == 1; }
+
 int64_t pair_tiles_per_launch(int pairs_per_tile, int threads) {
   int64_t t = ((static_cast<int64_t>(1) << 32) - 1) / (static_cast<int64_t>(pairs_per_tile) * threads);
   const int64_t by_blocks = ((static_cast<int64_t>(1) << 31) - 1) / pairs_per_tile;
   if (by_blocks < t) t = by_blocks;
-  const char* v = std::getenv("SPR_NCC_MAX_TILES");
-  if (v && *v) {
-    const long long cap = std::atoll(v);
-    if (cap >= 1 && cap < t) t = cap;
-  }
-  return t;
+  const int cap = env_int("SPR_NCC_MAX_TILES", 0);
+  return cap >= 1 && cap < t ? cap : t;
 }
 
 size_t prepared_query_item_bytes(const NccGeom& g, int method) {
@@ -66,20 +70,15 @@ size_t prepared_gallery_item_bytes(const NccGeom& g, int method) {
 struct spr_ncc_plan {
   spr::NccGeom geom;
   int method;              // resolved: SPR_NCC_FFT, SPR_NCC_DIRECT or SPR_NCC_MFMA
-  spr::cf* tw_h = nullptr;  // device: exp(-2*pi*i*k/nh), k < nh
-  spr::cf* tw_w = nullptr;  // device: exp(-2*pi*i*k/nw), k < nw
-  unsigned* team_sync = nullptr;  // device: arrival counters of the pair kernel's 8 workgroup teams
-  spr::FftWorkspace ws{nullptr, 0, nullptr};  // device: scratch of the "big" geometries (maps beyond LDS)
-  float* six_ctab = nullptr;  // device: pre-twist table of the six-wave pair kernel
-  float* mfma_x = nullptr;    // device: correction matrix of the matrix-core method's exact form (one call at a time per plan)
+  spr::PlanScratch scratch{};
   // A plan that owns device scratch its kernels write (mfma_x, team_sync, ws) orders its own calls: every scoring call
   // records `done` behind its launches, and a call that arrives on ANOTHER stream waits for it first - two streams sharing a
   // plan (one scorer, equal-shaped layers on separate streams) then serialise instead of racing on the scratch.
   hipEvent_t done = nullptr;
   hipStream_t last_stream = nullptr;
   bool used = false;
-  bool team_mode = false;  // SPR_NCC_TEAM at plan creation: the team schedule's counters are written by the kernels
-  bool owns_scratch() const { return mfma_x || ws.base || (team_sync && team_mode); }
+  // (the counters are written only by the team schedule: the same test as the launcher's, pair_t in ncc_fft.hip)
+  bool owns_scratch() const { return scratch.mfma_x || scratch.ws || (scratch.team_sync && spr::team_schedule()); }
 };
 
 // before / after the launches of a scoring call on stream s
@@ -162,9 +161,8 @@ extern "C" int spr_ncc_plan_create(const spr_ncc_shape* shape, spr_ncc_plan** pl
   NccGeom gf = g, gd = g;
   const bool fft_ok = fft_geometry(gf, shape->method == SPR_NCC_FFT_POW2), direct_ok = direct_geometry(gd);
   // SPR_NCC_MFMA=0 in the environment keeps SPR_NCC_AUTO off the matrix-core kernel (A/B runs)
-  const char* mfma_env = std::getenv("SPR_NCC_MFMA");
   NccGeom gm = g;
-  const bool mfma_ok = mfma_geometry(gm), mfma_auto = mfma_ok && !(mfma_env && mfma_env[0] == '0');
+  const bool mfma_ok = mfma_geometry(gm), mfma_auto = mfma_ok && env_int("SPR_NCC_MFMA", 1) != 0;
   if (shape->method == SPR_NCC_MFMA) {
     if (!mfma_ok) { set_error("matrix-core method: bfloat16 / float16 maps of 28x12 (cropped) on both sides only, got dtype %d, query %dx%d vs gallery %dx%d", g.dtype, g.th, g.tw, g.ih, g.iw); return SPR_ERR_UNSUPPORTED; }
     method = SPR_NCC_MFMA;
@@ -188,26 +186,27 @@ extern "C" int spr_ncc_plan_create(const spr_ncc_shape* shape, spr_ncc_plan** pl
   if (!p) { set_error("out of host memory"); return SPR_ERR_ARG; }
   p->method = method;
   p->geom = method == SPR_NCC_FFT ? gf : method == SPR_NCC_MFMA ? gm : gd;
+  PlanScratch& sc = p->scratch;
   if (method == SPR_NCC_MFMA && mfma_workspace_bytes(p->geom) > 0 &&
-      hipMalloc(reinterpret_cast<void**>(&p->mfma_x), mfma_workspace_bytes(p->geom)) != hipSuccess) {
+      hipMalloc(reinterpret_cast<void**>(&sc.mfma_x), mfma_workspace_bytes(p->geom)) != hipSuccess) {
     set_error("hipMalloc(%zu bytes of correction matrix) failed", mfma_workspace_bytes(p->geom));
     spr_ncc_plan_destroy(p);
     return SPR_ERR_WORKSPACE;
   }
   if (method == SPR_NCC_FFT) {
-    int rc = make_twiddles(p->geom.nh, &p->tw_h);
-    if (rc == SPR_OK) rc = make_twiddles(p->geom.nw, &p->tw_w);
-    if (rc == SPR_OK && hipMalloc(reinterpret_cast<void**>(&p->team_sync), sizeof(unsigned) * 8 * 32) != hipSuccess) {
+    int rc = make_twiddles(p->geom.nh, &sc.tw_h);
+    if (rc == SPR_OK) rc = make_twiddles(p->geom.nw, &sc.tw_w);
+    if (rc == SPR_OK && hipMalloc(reinterpret_cast<void**>(&sc.team_sync), sizeof(unsigned) * 8 * 32) != hipSuccess) {
       set_error("hipMalloc(team counters) failed");
       rc = SPR_ERR_HIP;
     }
     const size_t ws_bytes = fft_workspace_bytes(p->geom);
     if (rc == SPR_OK && ws_bytes > 0) {
-      if (hipMalloc(&p->ws.base, ws_bytes) != hipSuccess) {
+      if (hipMalloc(&sc.ws, ws_bytes) != hipSuccess) {
         set_error("hipMalloc(%zu bytes of FFT workspace) failed", ws_bytes);
         rc = SPR_ERR_WORKSPACE;
       } else {
-        p->ws.bytes = ws_bytes;
+        sc.ws_bytes = ws_bytes;
       }
     }
     if (rc == SPR_OK && p->geom.six) {
@@ -218,28 +217,23 @@ extern "C" int spr_ncc_plan_create(const spr_ncc_shape* shape, spr_ncc_plan** pl
         const double x = 3.14159265358979323846 * (static_cast<double>(k) / p->geom.nw + 0.25);
         host[k] = static_cast<float>(std::cos(x) / std::sin(x));
       }
-      if (hipMalloc(reinterpret_cast<void**>(&p->six_ctab), sizeof(float) * half) != hipSuccess ||
-          hipMemcpy(p->six_ctab, host.data(), sizeof(float) * half, hipMemcpyHostToDevice) != hipSuccess) {
+      if (hipMalloc(reinterpret_cast<void**>(&sc.six_ctab), sizeof(float) * half) != hipSuccess ||
+          hipMemcpy(sc.six_ctab, host.data(), sizeof(float) * half, hipMemcpyHostToDevice) != hipSuccess) {
         set_error("pre-twist table: hipMalloc / hipMemcpy failed");
         rc = SPR_ERR_HIP;
       }
-      p->ws.six_ctab = p->six_ctab;
     }
     if (rc != SPR_OK) { spr_ncc_plan_destroy(p); return rc; }
   }
-  { const char* t = std::getenv("SPR_NCC_TEAM"); p->team_mode = t && t[0] == '1'; }
   *plan_out = p;
   return SPR_OK;
 }
 
 extern "C" void spr_ncc_plan_destroy(spr_ncc_plan* plan) {
   if (!plan) return;
-  if (plan->tw_h) (void)hipFree(plan->tw_h);
-  if (plan->tw_w) (void)hipFree(plan->tw_w);
-  if (plan->team_sync) (void)hipFree(plan->team_sync);
-  if (plan->ws.base) (void)hipFree(plan->ws.base);
-  if (plan->six_ctab) (void)hipFree(plan->six_ctab);
-  if (plan->mfma_x) (void)hipFree(plan->mfma_x);
+  const PlanScratch& sc = plan->scratch;
+  for (void* dev : std::initializer_list<void*>{sc.tw_h, sc.tw_w, sc.team_sync, sc.ws, sc.six_ctab, sc.mfma_x})
+    if (dev) (void)hipFree(dev);
   if (plan->done) (void)hipEventDestroy(plan->done);
   delete plan;
 }
@@ -268,11 +262,10 @@ static int prepare(spr_ncc_plan* plan, bool is_query, const void* maps, int64_t 
   if (n < 0 || n > 65535) { set_error("%s: n = %lld outside [0, 65535] (call in chunks)", who, static_cast<long long>(n)); return SPR_ERR_ARG; }
   if (n == 0) return SPR_OK;
   if (!maps || !prepared) { set_error("%s: null pointer", who); return SPR_ERR_ARG; }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (plan->method == SPR_NCC_FFT)
-    return launch_prep_fft(plan->geom, is_query, maps, n, prepared, plan->tw_h, plan->tw_w, plan->ws, s);
-  if (plan->method == SPR_NCC_MFMA) return launch_prep_mfma(plan->geom, is_query, maps, n, prepared, s);
-  return launch_prep_direct(plan->geom, is_query, maps, n, prepared, s);
+  const PrepCall c{is_query, maps, n, prepared, static_cast<hipStream_t>(stream)};
+  if (plan->method == SPR_NCC_FFT) return launch_prep_fft(plan->geom, plan->scratch, c);
+  if (plan->method == SPR_NCC_MFMA) return launch_prep_mfma(plan->geom, plan->scratch, c);
+  return launch_prep_direct(plan->geom, plan->scratch, c);
 }
 
 extern "C" int spr_ncc_prepare_queries(spr_ncc_plan* plan, const void* maps, int64_t n, void* prepared,
@@ -284,6 +277,20 @@ extern "C" int spr_ncc_prepare_gallery(spr_ncc_plan* plan, const void* maps, int
   return prepare(plan, false, maps, n, prepared, stream, "spr_ncc_prepare_gallery");
 }
 
+// the launches of one scoring call, between plan_enter and plan_leave
+static int score_pairs(spr_ncc_plan* plan, const PairCall& c) {
+  int rc = plan_enter(plan, c.stream);
+  if (rc != SPR_OK) return rc;
+  if (plan->method == SPR_NCC_FFT)
+    rc = launch_pair_fft(plan->geom, plan->scratch, c);
+  else if (plan->method == SPR_NCC_MFMA)
+    rc = launch_pair_mfma(plan->geom, plan->scratch, c);
+  else
+    rc = launch_pair_direct(plan->geom, plan->scratch, c);
+  plan_leave(plan, c.stream);
+  return rc;
+}
+
 extern "C" int spr_ncc_score(spr_ncc_plan* plan, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores,
                              int64_t ld, int64_t col0, int accumulate_max, spr_stream_t stream) {
   if (!plan) { set_error("spr_ncc_score: null plan"); return SPR_ERR_ARG; }
@@ -291,32 +298,10 @@ extern "C" int spr_ncc_score(spr_ncc_plan* plan, const void* pq, int64_t nq, con
   if (nq == 0 || ng == 0) return SPR_OK;
   if (!pq || !pg || !scores) { set_error("spr_ncc_score: null pointer"); return SPR_ERR_ARG; }
   if (nq > 65535 || ng > (1 << 24)) { set_error("spr_ncc_score: too many items in one call (chunk the gallery)"); return SPR_ERR_ARG; }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  int rc = plan_enter(plan, s);
-  if (rc != SPR_OK) return rc;
-  if (plan->method == SPR_NCC_FFT)
-    rc = launch_pair_fft(plan->geom, pq, nq, pg, ng, scores, ld, col0, accumulate_max, nullptr, plan->tw_h,
-                         plan->tw_w, plan->team_sync, plan->ws, s);
-  else if (plan->method == SPR_NCC_MFMA)
-    rc = launch_pair_mfma(plan->geom, pq, nq, pg, ng, scores, ld, col0, accumulate_max, nullptr, plan->mfma_x, s);
-  else
-    rc = launch_pair_direct(plan->geom, pq, nq, pg, ng, scores, ld, col0, accumulate_max, nullptr, s);
-  plan_leave(plan, s);
-  return rc;
+  return score_pairs(plan, PairCall{pq, nq, pg, ng, scores, ld, col0, accumulate_max, nullptr, static_cast<hipStream_t>(stream)});
 }
 
 extern "C" int spr_ncc_maps(spr_ncc_plan* plan, const void* pq, const void* pg, float* maps_out, spr_stream_t stream) {
   if (!plan || !pq || !pg || !maps_out) { set_error("spr_ncc_maps: null pointer"); return SPR_ERR_ARG; }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  int rc = plan_enter(plan, s);
-  if (rc != SPR_OK) return rc;
-  if (plan->method == SPR_NCC_FFT)
-    rc = launch_pair_fft(plan->geom, pq, 1, pg, 1, nullptr, 1, 0, 0, maps_out, plan->tw_h, plan->tw_w,
-                         plan->geom.big ? plan->team_sync : nullptr, plan->ws, s);
-  else if (plan->method == SPR_NCC_MFMA)
-    rc = launch_pair_mfma(plan->geom, pq, 1, pg, 1, nullptr, 1, 0, 0, maps_out, plan->mfma_x, s);
-  else
-    rc = launch_pair_direct(plan->geom, pq, 1, pg, 1, nullptr, 1, 0, 0, maps_out, s);
-  plan_leave(plan, s);
-  return rc;
+  return score_pairs(plan, PairCall{pq, 1, pg, 1, nullptr, 1, 0, 0, maps_out, static_cast<hipStream_t>(stream)});
 }

@@ -187,53 +187,49 @@ bool direct_geometry(NccGeom& g) {
   return true;
 }
 
-int launch_prep_direct(const NccGeom& g, bool is_query, const void* maps, int64_t n, void* prepared,
-                       hipStream_t stream) {
-  if (n == 0) return SPR_OK;
-  const PrepLds l = is_query ? prep_lds(g.th, g.tw, false) : prep_lds(g.ih, g.iw, true);
+int launch_prep_direct(const NccGeom& g, const PlanScratch&, const PrepCall& c) {
+  if (c.n == 0) return SPR_OK;
+  const PrepLds l = c.is_query ? prep_lds(g.th, g.tw, false) : prep_lds(g.ih, g.iw, true);
   const size_t item_floats =
-      (is_query ? prepared_query_item_bytes(g, SPR_NCC_DIRECT) : prepared_gallery_item_bytes(g, SPR_NCC_DIRECT)) /
+      (c.is_query ? prepared_query_item_bytes(g, SPR_NCC_DIRECT) : prepared_gallery_item_bytes(g, SPR_NCC_DIRECT)) /
       sizeof(float);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(prep_direct_kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
-  hipLaunchKernelGGL(prep_direct_kernel, dim3(g.channels, static_cast<unsigned>(n)), dim3(kThreads), l.total, stream,
-                     g, is_query ? 1 : 0, maps, static_cast<float*>(prepared), item_floats,
+  hipLaunchKernelGGL(prep_direct_kernel, dim3(g.channels, static_cast<unsigned>(c.n)), dim3(kThreads), l.total, c.stream,
+                     g, c.is_query ? 1 : 0, c.maps, static_cast<float*>(c.prepared), item_floats,
                      static_cast<unsigned>(l.x0_off), static_cast<unsigned>(l.sat_off));
   return check_launch("prep_direct_kernel");
 }
 
 template <int SPT>
-static int launch_pair_direct_t(const NccGeom& g, const void* pq, int64_t nq, const void* pg, int64_t ng,
-                                float* scores, int64_t ld, int64_t col0, int accumulate, float* maps_out,
-                                hipStream_t stream) {
+static int launch_pair_direct_t(const NccGeom& g, const PlanScratch&, const PairCall& c) {
   const DirectLds l = direct_lds(g);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pair_direct_kernel<SPT>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
   // grid = (gallery, query) workgroups; HIP refuses 2^32 work-items and more along x: slices of the gallery
   const size_t g_item_floats = prepared_gallery_item_bytes(g, SPR_NCC_DIRECT) / sizeof(float);
   const int64_t max_g = pair_tiles_per_launch(1, kThreads);
-  for (int64_t g0 = 0; g0 < ng; g0 += max_g) {
-    const int64_t n = ng - g0 < max_g ? ng - g0 : max_g;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_direct_kernel<SPT>), dim3(static_cast<unsigned>(n), static_cast<unsigned>(nq)),
-                       dim3(kThreads), l.total, stream, g, static_cast<const float*>(pq),
+  for (int64_t g0 = 0; g0 < c.ng; g0 += max_g) {
+    const int64_t n = c.ng - g0 < max_g ? c.ng - g0 : max_g;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_direct_kernel<SPT>), dim3(static_cast<unsigned>(n), static_cast<unsigned>(c.nq)),
+                       dim3(kThreads), l.total, c.stream, g, static_cast<const float*>(c.pq),
                        prepared_query_item_bytes(g, SPR_NCC_DIRECT) / sizeof(float),
-                       static_cast<const float*>(pg) + static_cast<size_t>(g0) * g_item_floats, g_item_floats, scores,
-                       static_cast<long long>(ld), static_cast<long long>(col0 + g0), accumulate, maps_out, l.pws, l.tws,
-                       static_cast<unsigned>(l.t_off));
+                       static_cast<const float*>(c.pg) + static_cast<size_t>(g0) * g_item_floats, g_item_floats, c.scores,
+                       static_cast<long long>(c.ld), static_cast<long long>(c.col0 + g0), c.accumulate, c.maps_out, l.pws,
+                       l.tws, static_cast<unsigned>(l.t_off));
     const int rc = check_launch("pair_direct_kernel");
     if (rc != SPR_OK) return rc;
   }
   return SPR_OK;
 }
 
-int launch_pair_direct(const NccGeom& g, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores,
-                       int64_t ld, int64_t col0, int accumulate, float* maps_out, hipStream_t stream) {
-  if (nq == 0 || ng == 0) return SPR_OK;
+int launch_pair_direct(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
+  if (c.nq == 0 || c.ng == 0) return SPR_OK;
   switch (g.strips_per_thread) {
-    case 1: return launch_pair_direct_t<1>(g, pq, nq, pg, ng, scores, ld, col0, accumulate, maps_out, stream);
-    case 2: return launch_pair_direct_t<2>(g, pq, nq, pg, ng, scores, ld, col0, accumulate, maps_out, stream);
-    case 4: return launch_pair_direct_t<4>(g, pq, nq, pg, ng, scores, ld, col0, accumulate, maps_out, stream);
-    case 8: return launch_pair_direct_t<8>(g, pq, nq, pg, ng, scores, ld, col0, accumulate, maps_out, stream);
+    case 1: return launch_pair_direct_t<1>(g, s, c);
+    case 2: return launch_pair_direct_t<2>(g, s, c);
+    case 4: return launch_pair_direct_t<4>(g, s, c);
+    case 8: return launch_pair_direct_t<8>(g, s, c);
     default: set_error("direct NCC: unsupported strips per thread %d", g.strips_per_thread); return SPR_ERR_UNSUPPORTED;
   }
 }

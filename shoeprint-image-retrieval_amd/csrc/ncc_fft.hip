@@ -751,9 +751,8 @@ struct FftEntry {
   int spec_per_chan;
   size_t (*prep_lds_total)(const NccGeom&, bool);
   size_t (*pair_lds_total)(const NccGeom&);
-  int (*prep)(const NccGeom&, bool, const void*, int64_t, void*, const cf*, const cf*, const FftWorkspace&, hipStream_t);
-  int (*pair)(const NccGeom&, bool, const void*, int64_t, const void*, int64_t, float*, int64_t, int64_t, int, float*,
-              const cf*, const cf*, unsigned*, const FftWorkspace&, hipStream_t);
+  int (*prep)(const NccGeom&, const PlanScratch&, const PrepCall&);
+  int (*pair)(const NccGeom&, const PlanScratch&, const PairCall&);
   size_t (*prep_slot_bytes)(const NccGeom&, bool);
   size_t (*pair_slot_bytes)(const NccGeom&);
   bool big_only;  // grid whose working set never fits LDS: always the workspace ("big") kernels
@@ -776,64 +775,57 @@ template <class C>
 size_t pair_slot_bytes_t(const NccGeom& g) { return pair_fft_lds<C>(g).slot_bytes; }
 
 template <class C, bool BIG, int PT>
-int prep_launch(const NccGeom& g, bool is_query, const void* maps, int64_t n, void* prepared, const cf* tw_h,
-                const cf* tw_w, const FftWorkspace& ws, hipStream_t stream) {
-  const PrepFftLds l = prep_fft_lds<C>(g, is_query, PT);
-  const size_t item_bytes = is_query ? prepared_query_item_bytes(g, SPR_NCC_FFT) : prepared_gallery_item_bytes(g, SPR_NCC_FFT);
+int prep_launch(const NccGeom& g, const PlanScratch& s, const PrepCall& c) {
+  const PrepFftLds l = prep_fft_lds<C>(g, c.is_query, PT);
+  const size_t item_bytes = c.is_query ? prepared_query_item_bytes(g, SPR_NCC_FFT) : prepared_gallery_item_bytes(g, SPR_NCC_FFT);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(prep_fft_kernel<C, BIG, PT>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
   // big mode: one workspace slot per workgroup of a launch, so the items go in batches the workspace can hold
-  int64_t batch = n;
+  int64_t batch = c.n;
   if (BIG) {
     const size_t per_item = l.slot_bytes * static_cast<size_t>(g.channels);
-    if (!ws.base || ws.bytes < per_item) { set_error("prep_fft_kernel: workspace too small for one item"); return SPR_ERR_WORKSPACE; }
-    batch = static_cast<int64_t>(ws.bytes / per_item);
+    if (!s.ws || s.ws_bytes < per_item) { set_error("prep_fft_kernel: workspace too small for one item"); return SPR_ERR_WORKSPACE; }
+    batch = static_cast<int64_t>(s.ws_bytes / per_item);
   }
-  const int raw_h = is_query ? g.q_h : g.g_h, raw_w = is_query ? g.q_w : g.g_w;
+  const int raw_h = c.is_query ? g.q_h : g.g_h, raw_w = c.is_query ? g.q_w : g.g_w;
   const size_t elem = g.dtype == SPR_F32 ? 4 : 2;
   const size_t raw_item_bytes = static_cast<size_t>(g.channels) * raw_h * raw_w * elem;
-  for (int64_t first = 0; first < n; first += batch) {
-    const int64_t m = n - first < batch ? n - first : batch;
+  for (int64_t first = 0; first < c.n; first += batch) {
+    const int64_t m = c.n - first < batch ? c.n - first : batch;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(prep_fft_kernel<C, BIG, PT>), dim3(g.channels, static_cast<unsigned>(m)), dim3(PT),
-                       l.total, stream, g, is_query ? 1 : 0,
-                       static_cast<const void*>(static_cast<const unsigned char*>(maps) + first * raw_item_bytes),
-                       static_cast<unsigned char*>(prepared) + first * item_bytes, item_bytes, tw_h,
-                       tw_w, static_cast<unsigned>(l.x0_off), static_cast<unsigned>(l.f_off),
+                       l.total, c.stream, g, c.is_query ? 1 : 0,
+                       static_cast<const void*>(static_cast<const unsigned char*>(c.maps) + first * raw_item_bytes),
+                       static_cast<unsigned char*>(c.prepared) + first * item_bytes, item_bytes, s.tw_h,
+                       s.tw_w, static_cast<unsigned>(l.x0_off), static_cast<unsigned>(l.f_off),
                        static_cast<unsigned>(l.xbuf_off), static_cast<unsigned>(l.zbuf_off),
-                       static_cast<unsigned>(l.sat2_off), l.f_stride, static_cast<unsigned char*>(ws.base), l.slot_bytes);
+                       static_cast<unsigned>(l.sat2_off), l.f_stride, static_cast<unsigned char*>(s.ws), l.slot_bytes);
     const int rc = check_launch("prep_fft_kernel");
     if (rc != SPR_OK) return rc;
   }
   return SPR_OK;
 }
 template <class C>
-int prep_t(const NccGeom& g, bool is_query, const void* maps, int64_t n, void* prepared, const cf* tw_h, const cf* tw_w,
-           const FftWorkspace& ws, hipStream_t stream) {
+int prep_t(const NccGeom& g, const PlanScratch& s, const PrepCall& c) {
 #ifndef SPR_SAN_SUBSET
-  if (g.big) return prep_launch<C, true, kThreads>(g, is_query, maps, n, prepared, tw_h, tw_w, ws, stream);
+  if (g.big) return prep_launch<C, true, kThreads>(g, s, c);
 #endif
-  if (prep_threads<C>(g, is_query) == 512)
-    return prep_launch<C, false, 512>(g, is_query, maps, n, prepared, tw_h, tw_w, ws, stream);
-  return prep_launch<C, false, kThreads>(g, is_query, maps, n, prepared, tw_h, tw_w, ws, stream);
+  if (prep_threads<C>(g, c.is_query) == 512) return prep_launch<C, false, 512>(g, s, c);
+  return prep_launch<C, false, kThreads>(g, s, c);
 }
 
 constexpr int kTeamCounters = 8 * 32;  // one 128-byte line per team
 
-inline int env_int(const char* name, int fallback) {
-  const char* v = std::getenv(name);
-  return v && *v ? std::atoi(v) : fallback;
-}
-
 template <class C, int RR, int KW, int PF, int RK, bool BIG, bool TEAM>
-int pair_launch(const NccGeom& g, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores, int64_t ld,
-                int64_t col0, int accumulate, float* maps_out, const cf* tw_h, const cf* tw_w, unsigned* team_sync,
-                const FftWorkspace& ws, hipStream_t stream) {
+int pair_launch(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
+  const int64_t nq = c.nq, ng = c.ng;
+  // (spr_ncc_maps on an LDS-resident plan has never handed the kernel the counters; its tile schedule does not read them)
+  unsigned* team_sync = c.maps_out && !BIG ? nullptr : s.team_sync;
   const PairFftLds l = pair_fft_lds<C>(g);
   const int64_t tiles = static_cast<int64_t>(ceil_div(static_cast<int>(nq), kTileQ)) * ceil_div(static_cast<int>(ng), kTileG);
   PairArgs a{};
   a.channels = g.channels; a.nq = static_cast<int>(nq); a.ng = static_cast<int>(ng);
   a.ih = g.ih; a.iw = g.iw; a.r_rows = g.r_rows; a.r_stride = g.r_stride; a.rounds_r = g.rounds_r;
-  a.inv_per_chan = g.inv_per_chan; a.accumulate = accumulate;
+  a.inv_per_chan = g.inv_per_chan; a.accumulate = c.accumulate;
   const void* kernel = reinterpret_cast<const void*>(pair_fft_kernel<C, RR, KW, PF, RK, BIG, TEAM>);
   (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
   unsigned grid = 0;
@@ -846,7 +838,7 @@ int pair_launch(const NccGeom& g, const void* pq, int64_t nq, const void* pg, in
       per_cu > 0 && cus >= 8) {
     int team_size = cus / 8 * per_cu;
     if (BIG) {  // one workspace slot per resident workgroup: the persistent grid is the only launch form
-      const size_t slots = ws.base ? ws.bytes / l.slot_bytes : 0;
+      const size_t slots = s.ws ? s.ws_bytes / l.slot_bytes : 0;
       if (slots < 8) { set_error("pair_fft_kernel: workspace too small"); return SPR_ERR_WORKSPACE; }
       if (static_cast<size_t>(team_size) * 8 > slots) team_size = static_cast<int>(slots / 8);
     }
@@ -864,7 +856,7 @@ int pair_launch(const NccGeom& g, const void* pq, int64_t nq, const void* pg, in
       a.sync_every = env_int("SPR_NCC_TEAM_EVERY", BIG ? 0 : 32);
       if (a.sync_every < 0) a.sync_every = 0;
       grid = 8u * static_cast<unsigned>(team_size);
-      if (hipMemsetAsync(team_sync, 0, sizeof(unsigned) * kTeamCounters, stream) != hipSuccess) {
+      if (hipMemsetAsync(team_sync, 0, sizeof(unsigned) * kTeamCounters, c.stream) != hipSuccess) {
         set_error("hipMemsetAsync(team counters) failed");
         return SPR_ERR_HIP;
       }
@@ -881,12 +873,12 @@ int pair_launch(const NccGeom& g, const void* pq, int64_t nq, const void* pg, in
       grid = static_cast<unsigned>(n * kTileQ * kTileG);
     }
     hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_fft_kernel<C, RR, KW, PF, RK, BIG, TEAM>), dim3(grid),
-                       dim3(C::NT), l.total, stream, a, static_cast<const unsigned char*>(pq),
-                       prepared_query_item_bytes(g, SPR_NCC_FFT), static_cast<const unsigned char*>(pg),
-                       prepared_gallery_item_bytes(g, SPR_NCC_FFT), scores,
-                       static_cast<long long>(ld), static_cast<long long>(col0), maps_out, tw_h, tw_w,
+                       dim3(C::NT), l.total, c.stream, a, static_cast<const unsigned char*>(c.pq),
+                       prepared_query_item_bytes(g, SPR_NCC_FFT), static_cast<const unsigned char*>(c.pg),
+                       prepared_gallery_item_bytes(g, SPR_NCC_FFT), c.scores,
+                       static_cast<long long>(c.ld), static_cast<long long>(c.col0), c.maps_out, s.tw_h, s.tw_w,
                        static_cast<unsigned>(l.r_off), static_cast<unsigned>(l.xbuf_off),
-                       static_cast<unsigned>(l.nyq_off), team_sync, static_cast<unsigned char*>(ws.base), l.slot_bytes);
+                       static_cast<unsigned>(l.nyq_off), team_sync, static_cast<unsigned char*>(s.ws), l.slot_bytes);
     const int rc = check_launch("pair_fft_kernel");
     if (rc != SPR_OK) return rc;
   }
@@ -900,34 +892,20 @@ int pair_launch(const NccGeom& g, const void* pq, int64_t nq, const void* pg, in
 constexpr int kBigMidKw = 11, kBigMidRr = 4;
 // tuned variant: KW_A x RR_A with PFA prefetch buffers; general variant: everything kept, one buffer
 template <class C, int PFA, bool BIG, bool TEAM>
-int pair_tb(const NccGeom& g, bool tuned, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores,
-            int64_t ld, int64_t col0, int accumulate, float* maps_out, const cf* tw_h, const cf* tw_w,
-            unsigned* team_sync, const FftWorkspace& ws, hipStream_t stream) {
-  if (tuned)
-    return pair_launch<C, C::RR_A, C::KW_A, PFA, rk_tuned<C>(), BIG, TEAM>(g, pq, nq, pg, ng, scores, ld, col0, accumulate,
-                                                                           maps_out, tw_h, tw_w, team_sync, ws, stream);
+int pair_tb(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
+  if (g.tight) return pair_launch<C, C::RR_A, C::KW_A, PFA, rk_tuned<C>(), BIG, TEAM>(g, s, c);
   if constexpr (BIG) {  // the workspace instance's middle variant (fill_geometry): the widest map of its grid, 4 row rounds
-    if (g.keep_w == kBigMidKw)
-      return pair_launch<C, kBigMidRr, kBigMidKw, 1, 0, BIG, TEAM>(g, pq, nq, pg, ng, scores, ld, col0, accumulate, maps_out,
-                                                                   tw_h, tw_w, team_sync, ws, stream);
+    if (g.keep_w == kBigMidKw) return pair_launch<C, kBigMidRr, kBigMidKw, 1, 0, BIG, TEAM>(g, s, c);
   }
-  return pair_launch<C, C::RR_B, C::KW_B, 1, 0, BIG, TEAM>(g, pq, nq, pg, ng, scores, ld, col0, accumulate, maps_out,
-                                                           tw_h, tw_w, team_sync, ws, stream);
+  return pair_launch<C, C::RR_B, C::KW_B, 1, 0, BIG, TEAM>(g, s, c);
 }
 template <class C, int PFA>
-int pair_t(const NccGeom& g, bool tuned, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores,
-           int64_t ld, int64_t col0, int accumulate, float* maps_out, const cf* tw_h, const cf* tw_w,
-           unsigned* team_sync, const FftWorkspace& ws, hipStream_t stream) {
+int pair_t(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
 #ifndef SPR_SAN_SUBSET  // (the sanitizer build of the CPU emulation compiles the default schedule only)
-  if (g.big)
-    return pair_tb<C, PFA, true, true>(g, tuned, pq, nq, pg, ng, scores, ld, col0, accumulate, maps_out, tw_h, tw_w,
-                                       team_sync, ws, stream);
-  if (team_sync && !maps_out && env_int("SPR_NCC_TEAM", 0) == 1)
-    return pair_tb<C, PFA, false, true>(g, tuned, pq, nq, pg, ng, scores, ld, col0, accumulate, maps_out, tw_h, tw_w,
-                                        team_sync, ws, stream);
+  if (g.big) return pair_tb<C, PFA, true, true>(g, s, c);
+  if (s.team_sync && !c.maps_out && team_schedule()) return pair_tb<C, PFA, false, true>(g, s, c);
 #endif
-  return pair_tb<C, PFA, false, false>(g, tuned, pq, nq, pg, ng, scores, ld, col0, accumulate, maps_out, tw_h, tw_w,
-                                       team_sync, ws, stream);
+  return pair_tb<C, PFA, false, false>(g, s, c);
 }
 
 template <class C, int PFA, bool BIG_ONLY = false>
@@ -942,15 +920,10 @@ constexpr FftEntry entry() {
 // The six-wave pair kernel lives in ncc_pair6.hip; the prep kernel here writes its layouts (Cfg<..., SIX = 1>).
 size_t pair6_lds_total(const NccGeom&) { return pair6_lds_bytes(); }
 size_t no_slot_bytes(const NccGeom&) { return 0; }
-int pair6_t(const NccGeom& g, bool, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores, int64_t ld,
-            int64_t col0, int accumulate, float* maps_out, const cf* tw_h, const cf*, unsigned*, const FftWorkspace& ws,
-            hipStream_t stream) {
-  return launch_pair6(g, pq, nq, pg, ng, scores, ld, col0, accumulate, maps_out, tw_h, ws.six_ctab, stream);
-}
 template <class C>
 constexpr FftEntry entry6() {
   return FftEntry{C::NH, C::NW, C::EH, C::TGH, C::EW, C::TGW, C::NT, C::GW::SPL, 0, 0, 0, 0, 0, false,
-                  C::kSpecPerChan, prep_lds_total_t<C>, pair6_lds_total, prep_t<C>, pair6_t,
+                  C::kSpecPerChan, prep_lds_total_t<C>, pair6_lds_total, prep_t<C>, launch_pair6,
                   prep_slot_bytes_t<C>, no_slot_bytes, false, true};
 }
 
@@ -1081,21 +1054,18 @@ size_t fft_workspace_bytes(const NccGeom& g) {
   return prep > pair ? prep : pair;
 }
 
-int launch_prep_fft(const NccGeom& g, bool is_query, const void* maps, int64_t n, void* prepared, const cf* tw_h,
-                    const cf* tw_w, const FftWorkspace& ws, hipStream_t stream) {
-  if (n == 0) return SPR_OK;
+int launch_prep_fft(const NccGeom& g, const PlanScratch& s, const PrepCall& c) {
+  if (c.n == 0) return SPR_OK;
   const FftEntry* e = find_entry(g.nh, g.nw, g.six);
   if (!e) { set_error("no FFT kernel for grid %dx%d", g.nh, g.nw); return SPR_ERR_UNSUPPORTED; }
-  return e->prep(g, is_query, maps, n, prepared, tw_h, tw_w, ws, stream);
+  return e->prep(g, s, c);
 }
 
-int launch_pair_fft(const NccGeom& g, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores,
-                    int64_t ld, int64_t col0, int accumulate, float* maps_out, const cf* tw_h, const cf* tw_w,
-                    unsigned* team_sync, const FftWorkspace& ws, hipStream_t stream) {
-  if (nq == 0 || ng == 0) return SPR_OK;
+int launch_pair_fft(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
+  if (c.nq == 0 || c.ng == 0) return SPR_OK;
   const FftEntry* e = find_entry(g.nh, g.nw, g.six);
   if (!e) { set_error("no FFT kernel for grid %dx%d", g.nh, g.nw); return SPR_ERR_UNSUPPORTED; }
-  return e->pair(g, g.tight != 0, pq, nq, pg, ng, scores, ld, col0, accumulate, maps_out, tw_h, tw_w, team_sync, ws, stream);
+  return e->pair(g, s, c);
 }
 
 #ifdef SPR_PREP_STAMPS

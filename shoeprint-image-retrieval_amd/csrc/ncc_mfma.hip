@@ -1030,8 +1030,7 @@ bool mfma_geometry(NccGeom& g) {
   if (!mfma_shape_ok(g)) return false;
   g.mfma_general = mfma_tuned_shape(g) ? 0 : 1;
   // SPR_NCC_MFMA_EXACT=0: the centred search map as hi + lo (two MFMAs per tile step, no correction matrix)
-  const char* e = std::getenv("SPR_NCC_MFMA_EXACT");
-  g.mfma_exact = !(e && e[0] == '0') || g.dtype == SPR_F16;  // half-precision maps: the exact form only (both operands raw)
+  g.mfma_exact = env_int("SPR_NCC_MFMA_EXACT", 1) != 0 || g.dtype == SPR_F16;  // half-precision maps: the exact form only (both operands raw)
   // buffer-load offsets of a 64-query block and the scalar channel offsets are 32-bit
   return mfma_query_item_bytes(g) * 64 < (static_cast<size_t>(1) << 31);
 }
@@ -1055,104 +1054,88 @@ size_t mfma_workspace_bytes(const NccGeom& g) {
 }
 
 template <class M>
-static int launch_prep_mfma_m(const NccGeom& g, bool is_query, const void* maps, int64_t n, void* prepared, hipStream_t stream) {
+static int launch_prep_mfma_m(const NccGeom& g, const PlanScratch&, const PrepCall& c) {
   constexpr int kMaxPix = MPrepSizes<M>::kMaxPix, kSatElems = MPrepSizes<M>::kSatElems;
   const size_t lds = align_up(64 + sizeof(float) * kMaxPix, 16) + 2 * sizeof(double) * kSatElems;
-  const size_t item_bytes = is_query ? mfma_query_item_bytes(g) : mfma_gallery_item_bytes(g);
+  const size_t item_bytes = c.is_query ? mfma_query_item_bytes(g) : mfma_gallery_item_bytes(g);
+  unsigned char* prepared = static_cast<unsigned char*>(c.prepared);
+  const unsigned n = static_cast<unsigned>(c.n);
   constexpr bool kFixed = M::FH == M::TH;  // (the equal-size instance is only chosen for template = map = frame)
   int rc;
-  static const bool general_prep = std::getenv("SPR_MFMA_PREP") && std::atoi(std::getenv("SPR_MFMA_PREP")) == 0;  // A/B switch
-  if constexpr (kFixed) {
-    if (!is_query && !general_prep) {  // the gallery of the equal-size instance: two channels per wave, no tables
+  if (!c.is_query && env_int("SPR_MFMA_PREP", 1) != 0) {  // (SPR_MFMA_PREP=0: the galleries too go through the kernel of the queries, an A/B switch)
+    if constexpr (kFixed) {  // the gallery of the equal-size instance: two channels per wave, no tables
       auto fixed = g.mfma_exact ? prep_gallery_fixed_kernel<M, true> : prep_gallery_fixed_kernel<M, false>;
-      hipLaunchKernelGGL(fixed, dim3((g.channels + 1) / 2, static_cast<unsigned>(n)), dim3(64), 0, stream, g, maps,
-                         static_cast<unsigned char*>(prepared), item_bytes);
+      hipLaunchKernelGGL(fixed, dim3((g.channels + 1) / 2, n), dim3(64), 0, c.stream, g, c.maps, prepared, item_bytes);
       rc = check_launch("prep_gallery_fixed_kernel");
-      if (rc == SPR_OK && g.mfma_exact) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(vcol_mfma_kernel<M>), dim3((pad16(g.channels) + 31) / 32, static_cast<unsigned>(n)),
-                           dim3(kThreads), 0, stream, g.channels, static_cast<unsigned char*>(prepared), item_bytes);
-        rc = check_launch("vcol_mfma_kernel");
-      }
-      return rc;
-    }
-  }
-  if constexpr (!kFixed) {
-    if (!is_query && !general_prep) {  // the gallery of the general instance: the same scheme with run-time windows
+    } else {  // the gallery of the general instance: the same scheme with run-time windows
       auto wave = g.mfma_exact ? prep_gallery_wave_kernel<M, true> : prep_gallery_wave_kernel<M, false>;
-      hipLaunchKernelGGL(wave, dim3((g.channels + 1) / 2, static_cast<unsigned>(n)), dim3(64), 0, stream, g, maps,
-                         static_cast<unsigned char*>(prepared), item_bytes);
+      hipLaunchKernelGGL(wave, dim3((g.channels + 1) / 2, n), dim3(64), 0, c.stream, g, c.maps, prepared, item_bytes);
       rc = check_launch("prep_gallery_wave_kernel");
-      if (rc == SPR_OK && g.mfma_exact) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(vcol_mfma_kernel<M>), dim3((pad16(g.channels) + 31) / 32, static_cast<unsigned>(n)),
-                           dim3(kThreads), 0, stream, g.channels, static_cast<unsigned char*>(prepared), item_bytes);
-        rc = check_launch("vcol_mfma_kernel");
-      }
-      return rc;
     }
+  } else {
+    auto kernel = g.mfma_exact ? prep_mfma_kernel<M, true, kFixed> : prep_mfma_kernel<M, false, kFixed>;
+    // one wave per (item, channel): maps of 336 pixels leave a 256-lane workgroup waiting at its ~20 barriers
+    hipLaunchKernelGGL(kernel, dim3(g.channels, n), dim3(64), lds, c.stream, g, c.is_query ? 1 : 0, c.maps, prepared, item_bytes);
+    rc = check_launch("prep_mfma_kernel");
   }
-  auto kernel = g.mfma_exact ? prep_mfma_kernel<M, true, kFixed> : prep_mfma_kernel<M, false, kFixed>;
-  // one wave per (item, channel): maps of 336 pixels leave a 256-lane workgroup waiting at its ~20 barriers
-  hipLaunchKernelGGL(kernel, dim3(g.channels, static_cast<unsigned>(n)), dim3(64), lds, stream, g, is_query ? 1 : 0, maps,
-                     static_cast<unsigned char*>(prepared), item_bytes);
-  rc = check_launch("prep_mfma_kernel");
-  if (rc == SPR_OK && g.mfma_exact && !is_query) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(vcol_mfma_kernel<M>), dim3((pad16(g.channels) + 31) / 32, static_cast<unsigned>(n)),
-                       dim3(kThreads), 0, stream, g.channels, static_cast<unsigned char*>(prepared), item_bytes);
+  if (rc == SPR_OK && g.mfma_exact && !c.is_query) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(vcol_mfma_kernel<M>), dim3((pad16(g.channels) + 31) / 32, n), dim3(kThreads), 0,
+                       c.stream, g.channels, prepared, item_bytes);
     rc = check_launch("vcol_mfma_kernel");
   }
   return rc;
 }
 
-int launch_prep_mfma(const NccGeom& g, bool is_query, const void* maps, int64_t n, void* prepared, hipStream_t stream) {
-  if (n == 0) return SPR_OK;
-  return with_instance(g, [&](auto m) { return launch_prep_mfma_m<decltype(m)>(g, is_query, maps, n, prepared, stream); });
+int launch_prep_mfma(const NccGeom& g, const PlanScratch& s, const PrepCall& c) {
+  if (c.n == 0) return SPR_OK;
+  return with_instance(g, [&](auto m) { return launch_prep_mfma_m<decltype(m)>(g, s, c); });
 }
 
 template <class M, bool EXACT, bool F16>
-static int launch_pair_mfma_t(const NccGeom& g, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores,
-                              int64_t ld, int64_t col0, int accumulate, float* maps_out, float* xws, hipStream_t stream) {
-  auto kernel = maps_out ? pair_mfma_kernel<M, true, EXACT, F16> : pair_mfma_kernel<M, false, EXACT, F16>;
+static int launch_pair_mfma_t(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
+  auto kernel = c.maps_out ? pair_mfma_kernel<M, true, EXACT, F16> : pair_mfma_kernel<M, false, EXACT, F16>;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
   const size_t q_item = mfma_query_item_bytes(g), g_item = mfma_gallery_item_bytes(g);
-  const unsigned char* pqb = static_cast<const unsigned char*>(pq);
-  const unsigned char* pgb = static_cast<const unsigned char*>(pg);
-  if (!EXACT || maps_out) {
-    const unsigned q_blocks = static_cast<unsigned>((nq + 63) / 64);
+  const unsigned char* pqb = static_cast<const unsigned char*>(c.pq);
+  const unsigned char* pgb = static_cast<const unsigned char*>(c.pg);
+  if (!EXACT || c.maps_out) {
+    const unsigned q_blocks = static_cast<unsigned>((c.nq + 63) / 64);
     // HIP refuses a grid of 2^32 work-items or more: slices of the gallery
     int64_t max_g = pair_tiles_per_launch(1, kThreads) / q_blocks;
     if (max_g < 1) max_g = 1;
-    for (int64_t g0 = 0; g0 < ng; g0 += max_g) {
-      const int64_t n = ng - g0 < max_g ? ng - g0 : max_g;
-      MfmaArgs a{g.channels, static_cast<int>(nq), static_cast<int>(n), static_cast<long long>(ld),
-                 static_cast<long long>(col0 + g0), accumulate, static_cast<unsigned>(q_item), static_cast<unsigned>(g_item),
-                 nullptr, 0, g.ih, g.iw};
-      hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(n), q_blocks), dim3(kThreads), M::kLdsBytes, stream, a, pqb,
-                         pgb + static_cast<size_t>(g0) * g_item, scores, maps_out);
+    for (int64_t g0 = 0; g0 < c.ng; g0 += max_g) {
+      const int64_t n = c.ng - g0 < max_g ? c.ng - g0 : max_g;
+      MfmaArgs a{g.channels, static_cast<int>(c.nq), static_cast<int>(n), static_cast<long long>(c.ld),
+                 static_cast<long long>(c.col0 + g0), c.accumulate, static_cast<unsigned>(q_item),
+                 static_cast<unsigned>(g_item), nullptr, 0, g.ih, g.iw};
+      hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(n), q_blocks), dim3(kThreads), M::kLdsBytes, c.stream, a, pqb,
+                         pgb + static_cast<size_t>(g0) * g_item, c.scores, c.maps_out);
       const int rc = check_launch("pair_mfma_kernel");
       if (rc != SPR_OK) return rc;
     }
     return SPR_OK;
   }
   // exact form: per block of 64 queries and slice of the gallery, the correction matrix first, then the pairs
+  float* xws = s.mfma_x;
   if (!xws) { set_error("pair_mfma_kernel: the exact form needs the plan's correction matrix"); return SPR_ERR_ARG; }
   int64_t max_g = pair_tiles_per_launch(1, kThreads);
   if (max_g > kCorrItems) max_g = kCorrItems;
   const unsigned u_off = static_cast<unsigned>(static_cast<size_t>(g.channels) * (M::kQMapBytes + 8));
   const unsigned v_off = static_cast<unsigned>(static_cast<size_t>(g.channels) * M::kGChanBytes);
-  for (int64_t q0 = 0; q0 < nq; q0 += 64) {
-    const int nq_here = static_cast<int>(nq - q0 < 64 ? nq - q0 : 64);
-    for (int64_t g0 = 0; g0 < ng; g0 += max_g) {
-      const int n = static_cast<int>(ng - g0 < max_g ? ng - g0 : max_g);
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(corr_mfma_kernel<M>), dim3((n + 63) / 64, M::NPOS), dim3(kThreads), 0, stream,
+  for (int64_t q0 = 0; q0 < c.nq; q0 += 64) {
+    const int nq_here = static_cast<int>(c.nq - q0 < 64 ? c.nq - q0 : 64);
+    for (int64_t g0 = 0; g0 < c.ng; g0 += max_g) {
+      const int n = static_cast<int>(c.ng - g0 < max_g ? c.ng - g0 : max_g);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(corr_mfma_kernel<M>), dim3((n + 63) / 64, M::NPOS), dim3(kThreads), 0, c.stream,
                          g.channels, nq_here, n, pqb + static_cast<size_t>(q0) * q_item, static_cast<unsigned>(q_item), u_off,
                          pgb + static_cast<size_t>(g0) * g_item, static_cast<unsigned>(g_item), v_off, xws, n);
       int rc = check_launch("corr_mfma_kernel");
       if (rc != SPR_OK) return rc;
-      MfmaArgs a{g.channels, nq_here, n, static_cast<long long>(ld), static_cast<long long>(col0 + g0), accumulate,
+      MfmaArgs a{g.channels, nq_here, n, static_cast<long long>(c.ld), static_cast<long long>(c.col0 + g0), c.accumulate,
                  static_cast<unsigned>(q_item), static_cast<unsigned>(g_item), xws, n, g.ih, g.iw};
-      hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(n), 1), dim3(kThreads), M::kLdsBytes, stream, a,
+      hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(n), 1), dim3(kThreads), M::kLdsBytes, c.stream, a,
                          pqb + static_cast<size_t>(q0) * q_item, pgb + static_cast<size_t>(g0) * g_item,
-                         scores ? scores + static_cast<size_t>(q0) * ld : nullptr, maps_out);
+                         c.scores ? c.scores + static_cast<size_t>(q0) * c.ld : nullptr, c.maps_out);
       rc = check_launch("pair_mfma_kernel");
       if (rc != SPR_OK) return rc;
     }
@@ -1160,15 +1143,12 @@ static int launch_pair_mfma_t(const NccGeom& g, const void* pq, int64_t nq, cons
   return SPR_OK;
 }
 
-int launch_pair_mfma(const NccGeom& g, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores, int64_t ld,
-                     int64_t col0, int accumulate, float* maps_out, float* xws, hipStream_t stream) {
-  if (nq == 0 || ng == 0) return SPR_OK;
+int launch_pair_mfma(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
+  if (c.nq == 0 || c.ng == 0) return SPR_OK;
   return with_instance(g, [&](auto m) {
     using M = decltype(m);
-    if (g.dtype == SPR_F16)
-      return launch_pair_mfma_t<M, true, true>(g, pq, nq, pg, ng, scores, ld, col0, accumulate, maps_out, xws, stream);
-    return g.mfma_exact ? launch_pair_mfma_t<M, true, false>(g, pq, nq, pg, ng, scores, ld, col0, accumulate, maps_out, xws, stream)
-                        : launch_pair_mfma_t<M, false, false>(g, pq, nq, pg, ng, scores, ld, col0, accumulate, maps_out, xws, stream);
+    if (g.dtype == SPR_F16) return launch_pair_mfma_t<M, true, true>(g, s, c);
+    return g.mfma_exact ? launch_pair_mfma_t<M, true, false>(g, s, c) : launch_pair_mfma_t<M, false, false>(g, s, c);
   });
 }
 

@@ -506,21 +506,20 @@ size_t pair6_lds_bytes() { return Six<C6>::kLdsBytes; }
 int pair6_max_rows() { return C6::kRows6; }
 int pair6_max_cols() { return 64; }  // outputs x[2m], x[2m+1] for m < 32
 
-int launch_pair6(const NccGeom& g, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores, int64_t ld,
-                 int64_t col0, int accumulate, float* maps_out, const cf* tw_h, const float* ctab, hipStream_t stream) {
-  if (nq == 0 || ng == 0) return SPR_OK;
-  if (!ctab) { set_error("pair6_kernel: the plan has no pre-twist table"); return SPR_ERR_ARG; }
+int launch_pair6(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
+  if (c.nq == 0 || c.ng == 0) return SPR_OK;
+  if (!s.six_ctab) { set_error("pair6_kernel: the plan has no pre-twist table"); return SPR_ERR_ARG; }
   using S = Six<C6>;
   Pair6Args a{};
-  a.channels = g.channels; a.nq = static_cast<int>(nq); a.ng = static_cast<int>(ng);
-  a.ih = g.ih; a.iw = g.iw; a.inv_per_chan = g.inv_per_chan; a.accumulate = accumulate;
-  a.tiles_g = ceil_div(static_cast<int>(ng), kTileG6);
+  a.channels = g.channels; a.nq = static_cast<int>(c.nq); a.ng = static_cast<int>(c.ng);
+  a.ih = g.ih; a.iw = g.iw; a.inv_per_chan = g.inv_per_chan; a.accumulate = c.accumulate;
+  a.tiles_g = ceil_div(static_cast<int>(c.ng), kTileG6);
   a.q_flags_off = static_cast<unsigned>(sizeof(cf) * static_cast<size_t>(g.channels) * g.spec_per_chan);
   a.g_flags_off = static_cast<unsigned>(static_cast<size_t>(g.channels) * (sizeof(cf) * g.spec_per_chan + sizeof(float) * g.inv_per_chan));
   if (g.channels > 1024) { set_error("pair6_kernel: at most 1024 channels"); return SPR_ERR_UNSUPPORTED; }
   const size_t lds_bytes = S::kLdsBytes + 2 * sizeof(unsigned short) * static_cast<size_t>(g.channels);
-  { const char* v = std::getenv("SPR_P6_PRIO"); a.prio_mode = v && *v ? std::atoi(v) : 2; }
-  const int64_t tiles = static_cast<int64_t>(ceil_div(static_cast<int>(nq), kTileQ6)) * a.tiles_g;
+  a.prio_mode = env_int("SPR_P6_PRIO", 2);
+  const int64_t tiles = static_cast<int64_t>(ceil_div(static_cast<int>(c.nq), kTileQ6)) * a.tiles_g;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pair6_kernel<C6>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             kLdsLimit);
   // HIP refuses grids of 2^32 work-items and more: launch in slices of pair tiles
@@ -529,10 +528,10 @@ int launch_pair6(const NccGeom& g, const void* pq, int64_t nq, const void* pg, i
     const int64_t n = tiles - t0 < max_tiles ? tiles - t0 : max_tiles;
     a.tile0 = static_cast<int>(t0);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(pair6_kernel<C6>), dim3(static_cast<unsigned>(n * (kTileQ6 * kTileG6 / 2))), dim3(2 * C6::NT),
-                       lds_bytes, stream, a, static_cast<const unsigned char*>(pq),
-                       prepared_query_item_bytes(g, SPR_NCC_FFT), static_cast<const unsigned char*>(pg),
-                       prepared_gallery_item_bytes(g, SPR_NCC_FFT), scores, static_cast<long long>(ld),
-                       static_cast<long long>(col0), maps_out, tw_h, ctab);
+                       lds_bytes, c.stream, a, static_cast<const unsigned char*>(c.pq),
+                       prepared_query_item_bytes(g, SPR_NCC_FFT), static_cast<const unsigned char*>(c.pg),
+                       prepared_gallery_item_bytes(g, SPR_NCC_FFT), c.scores, static_cast<long long>(c.ld),
+                       static_cast<long long>(c.col0), c.maps_out, s.tw_h, s.six_ctab);
     const int rc = check_launch("pair6_kernel");
     if (rc != SPR_OK) return rc;
   }

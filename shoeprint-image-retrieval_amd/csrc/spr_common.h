@@ -62,42 +62,54 @@ struct NccGeom {
 
 constexpr int kStrip = 8;  // output pixels per register strip in the direct kernel
 
-struct spr_ncc_plan_impl;
-
-// Launchers (each in its own .hip file).  All enqueue on `stream` and return SPR_OK / SPR_ERR_HIP.
-int launch_prep_direct(const NccGeom& g, bool is_query, const void* maps, int64_t n, void* prepared,
-                       hipStream_t stream);
-int launch_pair_direct(const NccGeom& g, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores,
-                       int64_t ld, int64_t col0, int accumulate, float* maps_out, hipStream_t stream);
-struct FftWorkspace {  // the plan's scratch for "big" FFT geometries (null / 0 otherwise)
-  void* base;
-  size_t bytes;
-  const float* six_ctab;  // six-wave pair kernel: its pre-twist table (nw/2 floats), null otherwise
+// One spr_ncc_score / spr_ncc_maps call, one spr_ncc_prepare_* call, and the device memory a plan owns: what api.hip hands
+// to the launchers below.  A launcher that slices a call passes a modified copy down.
+struct PairCall {
+  const void* pq; int64_t nq;
+  const void* pg; int64_t ng;
+  float* scores; int64_t ld, col0; int accumulate;
+  float* maps_out;  // spr_ncc_maps: the correlation map of the one pair; scores is null then
+  hipStream_t stream;
 };
-// six-wave pair kernel (ncc_pair6.hip)
-size_t pair6_lds_bytes();
-int pair6_max_rows();  // cropped search-map rows / columns it covers
-int pair6_max_cols();
-int launch_pair6(const NccGeom& g, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores, int64_t ld,
-                 int64_t col0, int accumulate, float* maps_out, const cf* tw_h, const float* ctab, hipStream_t stream);
+struct PrepCall {
+  bool is_query;
+  const void* maps; int64_t n;
+  void* prepared;
+  hipStream_t stream;
+};
+struct PlanScratch {      // null where the plan's method has none
+  cf* tw_h; cf* tw_w;     // FFT: exp(-2*pi*i*k/nh), k < nh, and the same for nw
+  unsigned* team_sync;    // FFT: 8 x 32 arrival counters of the pair kernel's workgroup teams
+  void* ws; size_t ws_bytes;  // FFT "big" geometries (maps beyond LDS): the working set
+  float* six_ctab;        // six-wave pair kernel: its pre-twist table (nw/2 floats)
+  float* mfma_x;          // matrix-core method, exact form: correction matrix (one call at a time per plan)
+};
+
+// The scorer's environment switches are all read through env_int: the method switches when a
+// plan is created (the *_geometry functions), the others at every launch.
+int env_int(const char* name, int fallback);  // the variable as an integer; `fallback` if unset or empty
+bool team_schedule();                          // SPR_NCC_TEAM=1: LDS-resident FFT plans score on the persistent team grid
+
+// Launchers (each method in its own .hip file).  All enqueue on the call's stream and return SPR_OK or an error code.
+int launch_prep_direct(const NccGeom& g, const PlanScratch& s, const PrepCall& c);
+int launch_pair_direct(const NccGeom& g, const PlanScratch& s, const PairCall& c);
+int launch_prep_fft(const NccGeom& g, const PlanScratch& s, const PrepCall& c);
+int launch_pair_fft(const NccGeom& g, const PlanScratch& s, const PairCall& c);
+int launch_pair6(const NccGeom& g, const PlanScratch& s, const PairCall& c);  // six-wave pair kernel (ncc_pair6.hip)
+int launch_prep_mfma(const NccGeom& g, const PlanScratch& s, const PrepCall& c);  // bf16 / f16 matrix cores (ncc_mfma.hip)
+int launch_pair_mfma(const NccGeom& g, const PlanScratch& s, const PairCall& c);
 // Pair kernels run one workgroup per pair in tiles of `pairs_per_tile`; HIP refuses a grid of 2^32 work-items or
 // more, so a launch takes at most this many tiles (SPR_NCC_MAX_TILES lowers it: tests of the slicing).
 int64_t pair_tiles_per_launch(int pairs_per_tile, int threads);
+
+size_t pair6_lds_bytes();
+int pair6_max_rows();  // cropped search-map rows / columns the six-wave kernel covers
+int pair6_max_cols();
 size_t fft_workspace_bytes(const NccGeom& g);  // what a plan with this geometry must allocate (0: none)
-int launch_prep_fft(const NccGeom& g, bool is_query, const void* maps, int64_t n, void* prepared, const cf* tw_h,
-                    const cf* tw_w, const FftWorkspace& ws, hipStream_t stream);
-int launch_pair_fft(const NccGeom& g, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores,
-                    int64_t ld, int64_t col0, int accumulate, float* maps_out, const cf* tw_h, const cf* tw_w,
-                    unsigned* team_sync, const FftWorkspace& ws,
-                    hipStream_t stream);  // team_sync: 8 x 32 counters, or null (tile mode only)
-// direct form on the bf16 matrix cores (ncc_mfma.hip): small maps stored as bfloat16
 bool mfma_geometry(NccGeom& g);  // true if an instantiated kernel covers this plan (fills mfma_exact)
 size_t mfma_query_item_bytes(const NccGeom& g);
 size_t mfma_gallery_item_bytes(const NccGeom& g);
 size_t mfma_workspace_bytes(const NccGeom& g);  // the plan's correction matrix of the exact form (0: none)
-int launch_prep_mfma(const NccGeom& g, bool is_query, const void* maps, int64_t n, void* prepared, hipStream_t stream);
-int launch_pair_mfma(const NccGeom& g, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores, int64_t ld,
-                     int64_t col0, int accumulate, float* maps_out, float* xws, hipStream_t stream);
 bool fft_geometry(NccGeom& g, bool pow2_only);  // fills the FFT fields; false if no instantiated kernel fits
 bool direct_geometry(NccGeom& g);  // fills the direct fields; false if the maps do not fit LDS
 
