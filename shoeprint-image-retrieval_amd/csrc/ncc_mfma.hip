@@ -147,6 +147,44 @@ __device__ __forceinline__ float from_storage(unsigned bits, int dtype) {
   return static_cast<float>(c.h);
 }
 
+// ---- the formulas every preparation path shares (queries, galleries per wave, galleries through the tables) ---------------
+// v rounded to the storage type: of a channel mean, kappa - the candidate of the exact shift (see prep_mfma_kernel)
+__device__ __forceinline__ float storage_round(float v, int dtype) { return from_storage(to_storage(v, dtype), dtype); }
+__device__ __forceinline__ bool representable(float v, int dtype) { return storage_round(v, dtype) == v; }
+// a pixel as the matrix cores see it: as stored, or shifted by kappa (0: no exact shift)
+__device__ __forceinline__ unsigned shifted_bits(unsigned bits, float kappa, int dtype) {
+  return kappa == 0.0f ? bits : to_storage(from_storage(bits, dtype) - kappa, dtype);
+}
+// split form: v = hi + lo, two bfloat16 numbers in one word
+__device__ __forceinline__ unsigned hilo_word(float v) {
+  const unsigned hi = bf16_round(v);
+  return (hi << 16) | bf16_round(v - bf16_value(hi));
+}
+// [first, first + size) clipped to [0, limit]; the window 'same' mode lays on a centre starts size / 2 before it
+struct Span { int lo, hi; };
+__device__ __forceinline__ Span clip_span(int first, int size, int limit) {
+  const int last = first + size;
+  return Span{first < 0 ? 0 : (first > limit ? limit : first), last < 0 ? 0 : (last > limit ? limit : last)};
+}
+__device__ __forceinline__ Span window(int centre, int size, int limit) { return clip_span(centre - size / 2, size, limit); }
+// window sum of the raw map from the window sum s1 of the centred one
+__device__ __forceinline__ double raw_window_sum(double s1, float mean, Span rows, Span cols) {
+  return s1 + static_cast<double>(mean) * static_cast<double>((rows.hi - rows.lo) * (cols.hi - cols.lo));
+}
+// A prepared gallery item (Byte: unsigned char or const unsigned char).  Per channel b = 1/sigma, b * S (float) and the pixel
+// words hi|lo, NPOS of each; exact form: V[position][channel] behind the channels, then the channel means (both padded to 16)
+template <class M, class Byte>
+struct GalleryItem {
+  template <class T> using As = std::conditional_t<std::is_const_v<Byte>, const T, T>;
+  Byte* base;
+  int channels;
+  __device__ __forceinline__ As<float>* b(int c) const { return reinterpret_cast<As<float>*>(base + static_cast<size_t>(c) * M::kGChanBytes); }
+  __device__ __forceinline__ As<float>* bs(int c) const { return b(c) + M::NPOS; }
+  __device__ __forceinline__ As<unsigned>* hl(int c) const { return reinterpret_cast<As<unsigned>*>(b(c) + 2 * M::NPOS); }
+  __device__ __forceinline__ As<float>* V() const { return b(channels); }
+  __device__ __forceinline__ As<float>* means() const { return V() + static_cast<size_t>(M::NPOS) * pad16(channels); }
+};
+
 // LDS of the prep kernel: the centred map (template or search map, whichever is larger) and two float64 summed-area tables.
 // The equal-size instance holds exactly its 28 x 12 map (7.4 KB per wave-sized workgroup: 21 of them share a CU).
 template <class M>
@@ -198,18 +236,14 @@ prep_mfma_kernel(NccGeom g, int is_query, const void* __restrict__ maps, unsigne
   // mean - kappa the corrections: the same algebra, exact products as before, and the cancellation is gone.  Channels spread
   // over several binades fail the check and stay as they are: their mean / sigma is small.
   auto exact_shift = [&](size_t base, int raw_w, int h, int w, float mean) {  // returns kappa (0: no exact shift exists)
-    const float kappa = from_storage(to_storage(mean, g.dtype), g.dtype);
+    const float kappa = storage_round(mean, g.dtype);
     double bad = 0.0;
     for (int i = tid; i < h * w; i += wg_size()) {
       const int y = i / w, x = i - y * w;
       const float d = from_storage(raw[base + static_cast<size_t>(y + g.crop) * raw_w + (x + g.crop)], g.dtype) - kappa;
-      if (from_storage(to_storage(d, g.dtype), g.dtype) != d) bad += 1.0;
+      if (!representable(d, g.dtype)) bad += 1.0;
     }
     return block_sum(bad, red) == 0.0 ? kappa : 0.0f;
-  };
-  auto shifted_bits = [&](size_t idx, float kappa) -> unsigned {
-    const unsigned bits = raw[idx];
-    return kappa == 0.0f ? bits : to_storage(from_storage(bits, g.dtype) - kappa, g.dtype);
   };
   // the channel columns that pad U / V to a multiple of 16 are zero: the last channel's workgroup writes them
   auto store_column = [&](float* mat, int pos, float v) {
@@ -228,7 +262,7 @@ prep_mfma_kernel(NccGeom g, int is_query, const void* __restrict__ maps, unsigne
     for (int i = tid; i < M::FH * 16; i += wg_size()) {
       const int u = (i >> 4) - fy, v = (i & 15) - fx;
       rows[i] = (u >= 0 && u < th && v >= 0 && v < tw)
-                    ? static_cast<uint16_t>(shifted_bits(base + static_cast<size_t>(u + g.crop) * g.q_w + (v + g.crop), kappa))
+                    ? static_cast<uint16_t>(shifted_bits(raw[base + static_cast<size_t>(u + g.crop) * g.q_w + (v + g.crop)], kappa, g.dtype))
                     : static_cast<uint16_t>(0);
     }
     float* sc = reinterpret_cast<float*>(out_item + static_cast<size_t>(g.channels) * M::kQMapBytes);
@@ -243,11 +277,10 @@ prep_mfma_kernel(NccGeom g, int is_query, const void* __restrict__ maps, unsigne
       for (int i = tid; i < M::NPOS; i += wg_size()) {
         const int y = i / M::TW, x = i - y * M::TW;
         // taps (u, v) whose pixel (y + u - th/2, x + v - tw/2) lies inside the map
-        const int u0 = th / 2 - y > 0 ? th / 2 - y : 0, u1 = th / 2 - y + ih < th ? th / 2 - y + ih : th;
-        const int v0 = tw / 2 - x > 0 ? tw / 2 - x : 0, v1 = tw / 2 - x + iw < tw ? tw / 2 - x + iw : tw;
+        const Span u = clip_span(th / 2 - y, ih, th), v = clip_span(tw / 2 - x, iw, tw);
         double st0 = 0.0;
-        if (y < ih && x < iw && u1 > u0 && v1 > v0)
-          st0 = sat1[u1 * stride + v1] - sat1[u0 * stride + v1] - sat1[u1 * stride + v0] + sat1[u0 * stride + v0];
+        if (y < ih && x < iw && u.hi > u.lo && v.hi > v.lo)
+          st0 = sat1[u.hi * stride + v.hi] - sat1[u.lo * stride + v.hi] - sat1[u.hi * stride + v.lo] + sat1[u.lo * stride + v.lo];
         store_column(U, i, scale * static_cast<float>(st0));
       }
     }
@@ -257,27 +290,22 @@ prep_mfma_kernel(NccGeom g, int is_query, const void* __restrict__ maps, unsigne
     load_centred(maps, base, g.g_w, g.crop, ih, iw, g.dtype, x0, red, &mean);
     const float kappa = EXACT ? exact_shift(base, g.g_w, ih, iw, mean) : 0.0f;
     if constexpr (EXACT) mean -= kappa;  // from here on: the mean of the map as the matrix cores see it
-    float* eb = reinterpret_cast<float*>(out_item + static_cast<size_t>(c) * M::kGChanBytes);
-    float* ebs = eb + M::NPOS;
-    unsigned* hl = reinterpret_cast<unsigned*>(ebs + M::NPOS);
+    const GalleryItem<M, unsigned char> out{out_item, g.channels};
+    float* eb = out.b(c);
+    float* ebs = out.bs(c);
+    unsigned* hl = out.hl(c);
     for (int i = tid; i < M::NPOS; i += wg_size()) {
       const int y = i / M::TW, x = i - y * M::TW;
       const bool inside = y < ih && x < iw;
-      if constexpr (EXACT) {
-        hl[i] = inside ? shifted_bits(base + static_cast<size_t>(y + g.crop) * g.g_w + (x + g.crop), kappa) << 16 : 0u;
-      } else {
-        const float v = inside ? x0[y * iw + x] : 0.0f;
-        const unsigned hi = bf16_round(v);
-        const unsigned lo = bf16_round(v - bf16_value(hi));
-        hl[i] = (hi << 16) | lo;
-      }
+      if constexpr (EXACT)
+        hl[i] = inside ? shifted_bits(raw[base + static_cast<size_t>(y + g.crop) * g.g_w + (x + g.crop)], kappa, g.dtype) << 16 : 0u;
+      else
+        hl[i] = hilo_word(inside ? x0[y * iw + x] : 0.0f);
     }
     build_tables(ih, iw);
-    if constexpr (EXACT) {  // the mean of the channel, behind V: vcol_mfma_kernel turns b and the means into V[position][channel]
-      float* means = reinterpret_cast<float*>(out_item + static_cast<size_t>(g.channels) * M::kGChanBytes) +
-                     static_cast<size_t>(M::NPOS) * cp;
-      if (tid == 0) means[c] = mean;
-    }
+    // the mean of the channel, behind V: vcol_mfma_kernel turns b and the means into V[position][channel]
+    if constexpr (EXACT)
+      if (tid == 0) out.means()[c] = mean;
     const double inv_n = 1.0 / static_cast<double>(th * tw);
     for (int i = tid; i < M::NPOS; i += wg_size()) {
       const int y = i / M::TW, x = i - y * M::TW;
@@ -290,169 +318,39 @@ prep_mfma_kernel(NccGeom g, int is_query, const void* __restrict__ maps, unsigne
       const double s2 = window_sum(sat2, ih, iw, th, tw, y, x);
       const float inv = inv_sigma_from_sums(s1, s2, inv_n);
       eb[i] = inv;
-      if constexpr (EXACT) {
-        const int y0 = y - th / 2 > 0 ? y - th / 2 : 0, y1 = y - th / 2 + th < ih ? y - th / 2 + th : ih;
-        const int xa = x - tw / 2 > 0 ? x - tw / 2 : 0, xb = x - tw / 2 + tw < iw ? x - tw / 2 + tw : iw;
-        const double si = s1 + static_cast<double>(mean) * static_cast<double>((y1 - y0) * (xb - xa));  // window sum of the raw map
-        ebs[i] = inv * static_cast<float>(si);
-      } else {
-        ebs[i] = inv * static_cast<float>(s1);
-      }
+      ebs[i] = inv * static_cast<float>(EXACT ? raw_window_sum(s1, mean, window(y, th, ih), window(x, tw, iw)) : s1);
     }
   }
 }
 
-// ---- gallery preparation of the equal-size instance (template = map = frame): one wave = TWO channels -------------------
-// The general kernel above spends ~7 000 SIMD cycles on a 336-pixel map, most of them in the summed-area tables built for maps
-// of any size.  With template = map every window is a corner window - rows [max(0, y - TH/2), min(TH, y + TH/2)), columns
-// likewise - so the two window sums are a prefix or a suffix in either direction and no table is needed:
-//   lane = (channel of the pair, row): its 12 pixels stay in registers; the column-range sums of its row (float64 prefix, 12
-//   values per table) go to LDS; 48 lanes = (table, channel, column) run down the 28 rows (prefix, then the row-range sum of
-//   every y) and write them back in place; the row lanes pick their 2 x 12 window sums up again and finish 1/sigma, the raw
-//   window sum and the pixel words.  Same statistics as prep_mfma_kernel (float64 sums of float32 values and float32 squares,
-//   similarity.py:57-62), formed in another order: a few ulp of float64 apart.  grid = (ceil(channels / 2), items), 64 lanes.
-template <class M, bool EXACT>
-__global__ void __launch_bounds__(64)
-prep_gallery_fixed_kernel(NccGeom g, const void* __restrict__ maps, unsigned char* __restrict__ prepared, size_t item_bytes) {
-  constexpr int H = M::TH, W = M::TW, N = M::NPOS;
-  static_assert(H <= 32 && W % 4 == 0 && 4 * W <= 64 && M::FH == M::TH, "one row per lane, two channels per wave");
-  __shared__ double tab[2][2][H][W];
-  const int lane = static_cast<int>(threadIdx.x), half = lane >> 5, row = lane & 31;
-  const int c = 2 * static_cast<int>(blockIdx.x) + half;
-  const size_t item = blockIdx.y;
-  const bool valid = row < H && c < g.channels;
-  const int cc = c < g.channels ? c : g.channels - 1, rr = row < H ? row : H - 1;
-  const uint16_t* raw = static_cast<const uint16_t*>(maps) +
-                        ((item * g.channels + cc) * static_cast<size_t>(g.g_h) + (rr + g.crop)) * g.g_w + g.crop;
-  unsigned bits[W];
-#pragma unroll
-  for (int k = 0; k < W; ++k) bits[k] = raw[k];
-  float v[W];
-  double s = 0.0;
-#pragma unroll
-  for (int k = 0; k < W; ++k) {
-    v[k] = valid ? from_storage(bits[k], g.dtype) : 0.0f;
-    s += static_cast<double>(v[k]);
-  }
-#pragma unroll
-  for (int m = 16; m >= 1; m >>= 1) s += shfl_xor(s, m);  // over the 32 lanes of this channel
-  float mean = static_cast<float>(s / static_cast<double>(N));
-  // exact shift (see prep_mfma_kernel): kappa = the mean in the storage type, taken if x - kappa is representable everywhere
-  float kappa = 0.0f;
-  if constexpr (EXACT) {
-    kappa = from_storage(to_storage(mean, g.dtype), g.dtype);
-    int bad = 0;
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-      const float d = v[k] - kappa;
-      if (valid && from_storage(to_storage(d, g.dtype), g.dtype) != d) bad = 1;
-    }
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) bad |= shfl_xor(bad, m);
-    if (bad) kappa = 0.0f;
-  }
-  unsigned char* out_item = prepared + item * item_bytes;
-  float* eb = reinterpret_cast<float*>(out_item + static_cast<size_t>(cc) * M::kGChanBytes);
-  float* ebs = eb + N;
-  unsigned* hl = reinterpret_cast<unsigned*>(ebs + N);
-  float x0[W];
-  unsigned word[W];
-#pragma unroll
-  for (int k = 0; k < W; ++k) {
-    x0[k] = v[k] - mean;
-    if constexpr (EXACT) {
-      word[k] = (kappa == 0.0f ? bits[k] : to_storage(v[k] - kappa, g.dtype)) << 16;
-    } else {
-      const unsigned hi = bf16_round(x0[k]);
-      word[k] = (hi << 16) | bf16_round(x0[k] - bf16_value(hi));
-    }
-  }
-  if (valid) {
-#pragma unroll
-    for (int k = 0; k < W; k += 4)
-      *reinterpret_cast<u32x4*>(hl + row * W + k) = u32x4{word[k], word[k + 1], word[k + 2], word[k + 3]};
-  }
-  if constexpr (EXACT) {
-    mean -= kappa;  // from here on: the mean of the map as the matrix cores see it
-    if (valid && row == 0) {
-      float* means = reinterpret_cast<float*>(out_item + static_cast<size_t>(g.channels) * M::kGChanBytes) +
-                     static_cast<size_t>(N) * pad16(g.channels);
-      means[c] = mean;
-    }
-  }
-  // column-range sums of this row: window columns [max(0, x - W/2), min(W, x + W/2))
-  {
-    double p1[W + 1], p2[W + 1];
-    p1[0] = 0.0; p2[0] = 0.0;
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-      const float sq = x0[k] * x0[k];  // np.square keeps float32 (similarity.py:57)
-      p1[k + 1] = p1[k] + static_cast<double>(valid ? x0[k] : 0.0f);
-      p2[k + 1] = p2[k] + static_cast<double>(valid ? sq : 0.0f);
-    }
-    if (row < H) {
-#pragma unroll
-      for (int x = 0; x < W; ++x) {
-        const int a = x - W / 2 > 0 ? x - W / 2 : 0, b = x + W / 2 < W ? x + W / 2 : W;
-        tab[0][half][row][x] = p1[b] - p1[a];
-        tab[1][half][row][x] = p2[b] - p2[a];
-      }
-    }
-  }
-  __syncthreads();
-  if (lane < 4 * W) {  // (table, channel, column): down the rows
-    double* col = &tab[0][0][0][0] + (lane / W) * (H * W) + lane % W;
-    double P[H + 1];
-    P[0] = 0.0;
-#pragma unroll
-    for (int r = 0; r < H; ++r) P[r + 1] = P[r] + col[r * W];
-#pragma unroll
-    for (int y = 0; y < H; ++y) {
-      const int a = y - H / 2 > 0 ? y - H / 2 : 0, b = y + H / 2 < H ? y + H / 2 : H;
-      col[y * W] = P[b] - P[a];
-    }
-  }
-  __syncthreads();
-  if (!valid) return;
-  const double inv_n = 1.0 / static_cast<double>(N);
-  const int y0 = row - H / 2 > 0 ? row - H / 2 : 0, y1 = row + H / 2 < H ? row + H / 2 : H;
-  float o_b[W], o_bs[W];
-#pragma unroll
-  for (int x = 0; x < W; ++x) {
-    const double s1 = tab[0][half][row][x], s2 = tab[1][half][row][x];
-    const float inv = inv_sigma_from_sums(s1, s2, inv_n);
-    o_b[x] = inv;
-    if constexpr (EXACT) {
-      const int xa = x - W / 2 > 0 ? x - W / 2 : 0, xb = x + W / 2 < W ? x + W / 2 : W;
-      const double si = s1 + static_cast<double>(mean) * static_cast<double>((y1 - y0) * (xb - xa));  // raw window sum
-      o_bs[x] = inv * static_cast<float>(si);
-    } else {
-      o_bs[x] = inv * static_cast<float>(s1);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < W; k += 4) {
-    *reinterpret_cast<float4*>(eb + row * W + k) = float4{o_b[k], o_b[k + 1], o_b[k + 2], o_b[k + 3]};
-    *reinterpret_cast<float4*>(ebs + row * W + k) = float4{o_bs[k], o_bs[k + 1], o_bs[k + 2], o_bs[k + 3]};
-  }
-}
-
-// ---- gallery preparation of the general instance: the same two-channels-per-wave scheme for ANY template on any map of the
-// frame.  The windows are no longer corner windows (rows [y - th/2, y - th/2 + th) clipped to the map), so the range sums are
-// differences of INCLUSIVE prefixes picked at run-time positions: the prefixes go through LDS (a register array cannot be
-// indexed at run time without scratch) - along the row (written and read back by the same lane), then down the columns.
+// ---- gallery preparation of both instances: one wave = TWO channels ----------------------------------------------------
+// prep_mfma_kernel above spends ~7 000 SIMD cycles on a 336-pixel map, most of them in the summed-area tables built for maps
+// of any size.  Here lane = (channel of the pair, row): its 12 pixels stay in registers; the column-range sums of its row
+// (float64, 12 values per table) go to LDS; 48 lanes = (table, channel, column) run down the 28 rows; the row lanes pick their
+// 2 x 12 window sums up again and finish 1/sigma, the raw window sum and the pixel words.  Same statistics as prep_mfma_kernel
+// (float64 sums of float32 values and float32 squares, similarity.py:57-62), formed in another order: a few ulp of float64
+// apart.  grid = (ceil(channels / 2), items), 64 lanes.  The instances differ in how the two range sums are formed only:
+//   equal-size (kFixed: template = map = frame, all sizes compile-time constants): every window is a corner window - rows
+//     [max(0, y - TH/2), min(TH, y + TH/2)), columns likewise - so each range sum is a difference of two prefixes at
+//     compile-time positions: prefixes in REGISTERS, the column lanes write the row-range sum of every y back in place.
+//   general (any template on any map of the frame): rows [y - th/2, y - th/2 + th) clipped to the map at run time, so the range
+//     sums are differences of INCLUSIVE prefixes picked at run-time positions: the prefixes go through LDS (a register array
+//     cannot be indexed at run time without scratch) - along the row (written and read back by the same lane), then down
+//     the columns.
 template <class M, bool EXACT>
 __global__ void __launch_bounds__(64)
 prep_gallery_wave_kernel(NccGeom g, const void* __restrict__ maps, unsigned char* __restrict__ prepared, size_t item_bytes) {
-  constexpr int H = M::TH, W = M::TW, N = M::NPOS;
+  constexpr int H = M::TH, W = M::TW;
+  constexpr bool kFixed = MPrepSizes<M>::kFixed;
   static_assert(H <= 32 && W % 4 == 0 && 4 * W <= 64, "one row per lane, two channels per wave");
   __shared__ double tab[2][2][H][W];
-  const int th = g.th, tw = g.tw, ih = g.ih, iw = g.iw;
+  const int th = kFixed ? H : g.th, tw = kFixed ? W : g.tw, ih = kFixed ? H : g.ih, iw = kFixed ? W : g.iw;
   const int lane = static_cast<int>(threadIdx.x), half = lane >> 5, row = lane & 31;
   const int c = 2 * static_cast<int>(blockIdx.x) + half;
   const size_t item = blockIdx.y;
   const bool chan_ok = c < g.channels;
-  const bool in_map = row < ih && chan_ok;  // this lane holds a row of the map
+  const bool in_map = row < ih && chan_ok;    // this lane holds a row of the map
+  const bool frame_row = row < H && chan_ok;  // every row of the frame is written (zeros outside the map)
   const int cc = chan_ok ? c : g.channels - 1, rr = row < ih ? row : ih - 1;
   const uint16_t* raw = static_cast<const uint16_t*>(maps) +
                         ((item * g.channels + cc) * static_cast<size_t>(g.g_h) + (rr + g.crop)) * g.g_w + g.crop;
@@ -467,58 +365,65 @@ prep_gallery_wave_kernel(NccGeom g, const void* __restrict__ maps, unsigned char
     s += static_cast<double>(v[k]);
   }
 #pragma unroll
-  for (int m = 16; m >= 1; m >>= 1) s += shfl_xor(s, m);
+  for (int m = 16; m >= 1; m >>= 1) s += shfl_xor(s, m);  // over the 32 lanes of this channel
   float mean = static_cast<float>(s / static_cast<double>(ih * iw));
+  // exact shift (see prep_mfma_kernel): kappa = the mean in the storage type, taken if x - kappa is representable everywhere
   float kappa = 0.0f;
   if constexpr (EXACT) {
-    kappa = from_storage(to_storage(mean, g.dtype), g.dtype);
+    kappa = storage_round(mean, g.dtype);
     int bad = 0;
 #pragma unroll
-    for (int k = 0; k < W; ++k) {
-      const float d = v[k] - kappa;
-      if (in_map && k < iw && from_storage(to_storage(d, g.dtype), g.dtype) != d) bad = 1;
-    }
+    for (int k = 0; k < W; ++k)
+      if (in_map && k < iw && !representable(v[k] - kappa, g.dtype)) bad = 1;
 #pragma unroll
     for (int m = 16; m >= 1; m >>= 1) bad |= shfl_xor(bad, m);
     if (bad) kappa = 0.0f;
   }
-  unsigned char* out_item = prepared + item * item_bytes;
-  float* eb = reinterpret_cast<float*>(out_item + static_cast<size_t>(cc) * M::kGChanBytes);
-  float* ebs = eb + N;
-  unsigned* hl = reinterpret_cast<unsigned*>(ebs + N);
+  const GalleryItem<M, unsigned char> out{prepared + item * item_bytes, g.channels};
   float x0[W];
   unsigned word[W];
 #pragma unroll
   for (int k = 0; k < W; ++k) {
     const bool inside = in_map && k < iw;
     x0[k] = inside ? v[k] - mean : 0.0f;
-    if constexpr (EXACT) {
-      word[k] = inside ? (kappa == 0.0f ? bits[k] : to_storage(v[k] - kappa, g.dtype)) << 16 : 0u;
-    } else {
-      const unsigned hi = bf16_round(x0[k]);
-      word[k] = (hi << 16) | bf16_round(x0[k] - bf16_value(hi));
-    }
+    if constexpr (EXACT)
+      word[k] = inside ? shifted_bits(bits[k], kappa, g.dtype) << 16 : 0u;
+    else
+      word[k] = hilo_word(x0[k]);
   }
-  const bool frame_row = row < H && chan_ok;  // every row of the frame is written (zeros outside the map)
   if (frame_row) {
 #pragma unroll
     for (int k = 0; k < W; k += 4)
-      *reinterpret_cast<u32x4*>(hl + row * W + k) = u32x4{word[k], word[k + 1], word[k + 2], word[k + 3]};
+      *reinterpret_cast<u32x4*>(out.hl(cc) + row * W + k) = u32x4{word[k], word[k + 1], word[k + 2], word[k + 3]};
   }
   if constexpr (EXACT) {
-    mean -= kappa;
-    if (chan_ok && row == 0) {
-      float* means = reinterpret_cast<float*>(out_item + static_cast<size_t>(g.channels) * M::kGChanBytes) +
-                     static_cast<size_t>(N) * pad16(g.channels);
-      means[c] = mean;
-    }
+    mean -= kappa;  // from here on: the mean of the map as the matrix cores see it
+    if (chan_ok && row == 0) out.means()[c] = mean;
   }
-  // inclusive prefixes along the row -> LDS -> the column-range sums of the row, back in place
-  if (row < H) {
-    double r1 = 0.0, r2 = 0.0;
+  // column-range sums of this row -> tab
+  if constexpr (kFixed) {
+    static_assert(M::FH == M::TH, "corner windows: template = map = frame");
+    double p1[W + 1], p2[W + 1];
+    p1[0] = 0.0; p2[0] = 0.0;
 #pragma unroll
     for (int k = 0; k < W; ++k) {
       const float sq = x0[k] * x0[k];  // np.square keeps float32 (similarity.py:57)
+      p1[k + 1] = p1[k] + static_cast<double>(x0[k]);
+      p2[k + 1] = p2[k] + static_cast<double>(sq);
+    }
+    if (row < H) {
+#pragma unroll
+      for (int x = 0; x < W; ++x) {
+        const Span cols = window(x, W, W);
+        tab[0][half][row][x] = p1[cols.hi] - p1[cols.lo];
+        tab[1][half][row][x] = p2[cols.hi] - p2[cols.lo];
+      }
+    }
+  } else if (row < H) {  // inclusive prefixes along the row -> LDS -> the range sums, back in place
+    double r1 = 0.0, r2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const float sq = x0[k] * x0[k];
       r1 += static_cast<double>(x0[k]);
       r2 += static_cast<double>(sq);
       tab[0][half][row][k] = r1;
@@ -527,11 +432,9 @@ prep_gallery_wave_kernel(NccGeom g, const void* __restrict__ maps, unsigned char
     double c1[W], c2[W];
 #pragma unroll
     for (int x = 0; x < W; ++x) {
-      int xa = x - tw / 2, xb = xa + tw;
-      xa = xa < 0 ? 0 : (xa > iw ? iw : xa);
-      xb = xb < 0 ? 0 : (xb > iw ? iw : xb);
-      const double hi1 = xb > 0 ? tab[0][half][row][xb - 1] : 0.0, lo1 = xa > 0 ? tab[0][half][row][xa - 1] : 0.0;
-      const double hi2 = xb > 0 ? tab[1][half][row][xb - 1] : 0.0, lo2 = xa > 0 ? tab[1][half][row][xa - 1] : 0.0;
+      const Span cols = window(x, tw, iw);
+      const double hi1 = cols.hi > 0 ? tab[0][half][row][cols.hi - 1] : 0.0, lo1 = cols.lo > 0 ? tab[0][half][row][cols.lo - 1] : 0.0;
+      const double hi2 = cols.hi > 0 ? tab[1][half][row][cols.hi - 1] : 0.0, lo2 = cols.lo > 0 ? tab[1][half][row][cols.lo - 1] : 0.0;
       c1[x] = hi1 - lo1;
       c2[x] = hi2 - lo2;
     }
@@ -542,46 +445,43 @@ prep_gallery_wave_kernel(NccGeom g, const void* __restrict__ maps, unsigned char
     }
   }
   __syncthreads();
-  if (lane < 4 * W) {  // (table, channel, column): inclusive prefix down the rows, in place
+  if (lane < 4 * W) {  // (table, channel, column): down the rows, in place
     double* col = &tab[0][0][0][0] + (lane / W) * (H * W) + lane % W;
-    double P[H];
-    double run = 0.0;
+    double P[H + 1];
+    P[0] = 0.0;
 #pragma unroll
-    for (int r = 0; r < H; ++r) {
-      run += col[r * W];
-      P[r] = run;
+    for (int r = 0; r < H; ++r) P[r + 1] = P[r] + col[r * W];
+#pragma unroll
+    for (int y = 0; y < H; ++y) {
+      const Span rows = kFixed ? window(y, H, H) : Span{0, y + 1};  // the row-range sum of y, or the inclusive prefix
+      col[y * W] = P[rows.hi] - P[rows.lo];
     }
-#pragma unroll
-    for (int r = 0; r < H; ++r) col[r * W] = P[r];
   }
   __syncthreads();
   if (!frame_row) return;
   const double inv_n = 1.0 / static_cast<double>(th * tw);
-  int y0 = row - th / 2, y1 = y0 + th;
-  y0 = y0 < 0 ? 0 : (y0 > ih ? ih : y0);
-  y1 = y1 < 0 ? 0 : (y1 > ih ? ih : y1);
+  const Span rows = window(row, th, ih);
   float o_b[W], o_bs[W];
 #pragma unroll
   for (int x = 0; x < W; ++x) {
-    const double s1 = (y1 > 0 ? tab[0][half][y1 - 1][x] : 0.0) - (y0 > 0 ? tab[0][half][y0 - 1][x] : 0.0);
-    const double s2 = (y1 > 0 ? tab[1][half][y1 - 1][x] : 0.0) - (y0 > 0 ? tab[1][half][y0 - 1][x] : 0.0);
+    double s1, s2;
+    if constexpr (kFixed) {
+      s1 = tab[0][half][row][x];
+      s2 = tab[1][half][row][x];
+    } else {
+      s1 = (rows.hi > 0 ? tab[0][half][rows.hi - 1][x] : 0.0) - (rows.lo > 0 ? tab[0][half][rows.lo - 1][x] : 0.0);
+      s2 = (rows.hi > 0 ? tab[1][half][rows.hi - 1][x] : 0.0) - (rows.lo > 0 ? tab[1][half][rows.lo - 1][x] : 0.0);
+    }
     const bool inside = row < ih && x < iw;
     const float inv = inside ? inv_sigma_from_sums(s1, s2, inv_n) : 0.0f;
     o_b[x] = inv;
-    if constexpr (EXACT) {
-      int xa = x - tw / 2, xb = xa + tw;
-      xa = xa < 0 ? 0 : (xa > iw ? iw : xa);
-      xb = xb < 0 ? 0 : (xb > iw ? iw : xb);
-      const double si = s1 + static_cast<double>(mean) * static_cast<double>((y1 - y0) * (xb - xa));  // raw window sum
-      o_bs[x] = inside ? inv * static_cast<float>(si) : 0.0f;
-    } else {
-      o_bs[x] = inside ? inv * static_cast<float>(s1) : 0.0f;
-    }
+    const double sw = EXACT ? raw_window_sum(s1, mean, rows, window(x, tw, iw)) : s1;  // window sum of the raw / the centred map
+    o_bs[x] = inside ? inv * static_cast<float>(sw) : 0.0f;
   }
 #pragma unroll
   for (int k = 0; k < W; k += 4) {
-    *reinterpret_cast<float4*>(eb + row * W + k) = float4{o_b[k], o_b[k + 1], o_b[k + 2], o_b[k + 3]};
-    *reinterpret_cast<float4*>(ebs + row * W + k) = float4{o_bs[k], o_bs[k + 1], o_bs[k + 2], o_bs[k + 3]};
+    *reinterpret_cast<float4*>(out.b(cc) + row * W + k) = float4{o_b[k], o_b[k + 1], o_b[k + 2], o_b[k + 3]};
+    *reinterpret_cast<float4*>(out.bs(cc) + row * W + k) = float4{o_bs[k], o_bs[k + 1], o_bs[k + 2], o_bs[k + 3]};
   }
 }
 
@@ -593,16 +493,16 @@ vcol_mfma_kernel(int channels, unsigned char* __restrict__ prepared, size_t item
   __shared__ float tile[32][M::NPOS + 1];
   const int tid = static_cast<int>(threadIdx.x);
   const int cp = pad16(channels), c0 = static_cast<int>(blockIdx.x) * 32;
-  unsigned char* item = prepared + static_cast<size_t>(blockIdx.y) * item_bytes;
-  float* V = reinterpret_cast<float*>(item + static_cast<size_t>(channels) * M::kGChanBytes);
-  const float* means = V + static_cast<size_t>(M::NPOS) * cp;
+  const GalleryItem<M, unsigned char> item{prepared + static_cast<size_t>(blockIdx.y) * item_bytes, channels};
+  float* V = item.V();
+  const float* means = item.means();
   const int p1 = tid + kThreads < M::NPOS ? tid + kThreads : tid;  // second pixel of this work-item (or the first again)
   for (int cb = 0; cb < 32; cb += 8) {
     float v0[8], v1[8];  // eight channel rows in flight
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int c = c0 + cb + k < channels ? c0 + cb + k : channels - 1;
-      const float* b = reinterpret_cast<const float*>(item + static_cast<size_t>(c) * M::kGChanBytes);
+      const float* b = item.b(c);
       const float m = c0 + cb + k < channels ? means[c] : 0.0f;
       v0[k] = b[tid] * m;
       v1[k] = b[p1] * m;
@@ -696,17 +596,15 @@ pair_mfma_kernel(MfmaArgs g, const unsigned char* __restrict__ pq, const unsigne
   for (int i = tid; i < M::kLdsBytes / 16; i += kThreads) reinterpret_cast<float4*>(lds)[i] = float4{0.f, 0.f, 0.f, 0.f};
 
   // ---- gallery side: this lane stages pixels e0 = tid and e1 = tid + 256 of every channel ---------------------------
-  const unsigned char* g_item = pg + gi * static_cast<size_t>(g.g_item_bytes);
+  const GalleryItem<M, const unsigned char> g_item{pg + gi * static_cast<size_t>(g.g_item_bytes), g.channels};
   const bool has1 = tid + kThreads < M::NPOS;
   const int e1 = has1 ? tid + kThreads : tid;
   float st_b[2], st_bs[2];
   unsigned st_hl[2];
   auto stage_load = [&](int c) {
-    const float* cb = reinterpret_cast<const float*>(g_item + static_cast<size_t>(c) * M::kGChanBytes);
-    st_b[0] = cb[tid];                 st_b[1] = cb[e1];
-    st_bs[0] = cb[M::NPOS + tid];      st_bs[1] = cb[M::NPOS + e1];
-    st_hl[0] = __float_as_uint(cb[2 * M::NPOS + tid]);
-    st_hl[1] = __float_as_uint(cb[2 * M::NPOS + e1]);
+    st_b[0] = g_item.b(c)[tid];    st_b[1] = g_item.b(c)[e1];
+    st_bs[0] = g_item.bs(c)[tid];  st_bs[1] = g_item.bs(c)[e1];
+    st_hl[0] = g_item.hl(c)[tid];  st_hl[1] = g_item.hl(c)[e1];
   };
   // low half: byte offset of the pixel in copy 0 (row, column); high half: its column in the padded map
   auto pixel_base = [&](int e) {
@@ -852,7 +750,7 @@ pair_mfma_kernel(MfmaArgs g, const unsigned char* __restrict__ pq, const unsigne
               if constexpr (EXACT) {  // this channel's term of the contraction, for the one pair of spr_ncc_maps
                 const int cp = pad16(g.channels), pos = 16 * t + col;
                 const float* U = reinterpret_cast<const float*>(q_block + static_cast<size_t>(g.channels) * (M::kQMapBytes + 8));
-                const float* V = reinterpret_cast<const float*>(g_item + static_cast<size_t>(g.channels) * M::kGChanBytes);
+                const float* V = g_item.V();
                 m -= U[static_cast<size_t>(pos) * cp + chan] * V[static_cast<size_t>(pos) * cp + chan];
               }
               const int py = (16 * t + col) / M::TW, px = (16 * t + col) - py * M::TW;
@@ -1060,18 +958,12 @@ static int launch_prep_mfma_m(const NccGeom& g, const PlanScratch&, const PrepCa
   const size_t item_bytes = c.is_query ? mfma_query_item_bytes(g) : mfma_gallery_item_bytes(g);
   unsigned char* prepared = static_cast<unsigned char*>(c.prepared);
   const unsigned n = static_cast<unsigned>(c.n);
-  constexpr bool kFixed = M::FH == M::TH;  // (the equal-size instance is only chosen for template = map = frame)
+  constexpr bool kFixed = MPrepSizes<M>::kFixed;  // (the equal-size instance is only chosen for template = map = frame)
   int rc;
   if (!c.is_query && env_int("SPR_MFMA_PREP", 1) != 0) {  // (SPR_MFMA_PREP=0: the galleries too go through the kernel of the queries, an A/B switch)
-    if constexpr (kFixed) {  // the gallery of the equal-size instance: two channels per wave, no tables
-      auto fixed = g.mfma_exact ? prep_gallery_fixed_kernel<M, true> : prep_gallery_fixed_kernel<M, false>;
-      hipLaunchKernelGGL(fixed, dim3((g.channels + 1) / 2, n), dim3(64), 0, c.stream, g, c.maps, prepared, item_bytes);
-      rc = check_launch("prep_gallery_fixed_kernel");
-    } else {  // the gallery of the general instance: the same scheme with run-time windows
-      auto wave = g.mfma_exact ? prep_gallery_wave_kernel<M, true> : prep_gallery_wave_kernel<M, false>;
-      hipLaunchKernelGGL(wave, dim3((g.channels + 1) / 2, n), dim3(64), 0, c.stream, g, c.maps, prepared, item_bytes);
-      rc = check_launch("prep_gallery_wave_kernel");
-    }
+    auto wave = g.mfma_exact ? prep_gallery_wave_kernel<M, true> : prep_gallery_wave_kernel<M, false>;  // two channels per wave, no tables
+    hipLaunchKernelGGL(wave, dim3((g.channels + 1) / 2, n), dim3(64), 0, c.stream, g, c.maps, prepared, item_bytes);
+    rc = check_launch("prep_gallery_wave_kernel");
   } else {
     auto kernel = g.mfma_exact ? prep_mfma_kernel<M, true, kFixed> : prep_mfma_kernel<M, false, kFixed>;
     // one wave per (item, channel): maps of 336 pixels leave a 256-lane workgroup waiting at its ~20 barriers

@@ -209,6 +209,15 @@ def test_emu_matrix_core_method_split_form(monkeypatch):
     pc.check_mfma_method(emu_scorer, 3, 20, 2)
 
 
+def test_emu_matrix_core_table_prep(monkeypatch):
+    """SPR_MFMA_PREP=0: the galleries of both instances through prep_mfma_kernel (summed-area tables) instead of the
+    two-channels-per-wave kernel."""
+    monkeypatch.setenv("SPR_MFMA_PREP", "0")
+    pc.check_mfma_method(emu_scorer, 3, 18, 2)
+    pc.check_mfma_general_shapes(emu_scorer, channels=3, nq=2, ng=3)
+    pc.check_mfma_conditioning(emu_scorer)
+
+
 # ------------------------------------------------------------------------- real library: ABI only
 def _declared_symbols():
     text = open(os.path.join(ROOT, "include", "shoeprint_mi355x.h")).read()

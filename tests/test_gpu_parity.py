@@ -146,6 +146,15 @@ def test_matrix_core_method_split_form(lib, monkeypatch):
     pc.check_mfma_method(_make_scorer(lib), 256, 70, 3)
 
 
+def test_matrix_core_table_prep(lib, monkeypatch):
+    """SPR_MFMA_PREP=0: the galleries of both instances through prep_mfma_kernel (summed-area tables) instead of the
+    two-channels-per-wave kernel."""
+    monkeypatch.setenv("SPR_MFMA_PREP", "0")
+    pc.check_mfma_method(_make_scorer(lib), 64, 70, 4)
+    pc.check_mfma_general_shapes(_make_scorer(lib), channels=176, nq=5, ng=6)
+    pc.check_mfma_conditioning(_make_scorer(lib), channels=64)
+
+
 def test_matrix_core_method_large_gallery(lib, monkeypatch):
     """G = 1 100 (beyond one slice of the correction matrix) at the full ResNet50-layer3 shape [1024,32,16] bfloat16 (BASELINE config 3 in shape): the matrix-core form
     against the FFT form on every pair, against the oracle on sampled pairs, identical ranks, launches sliced."""
