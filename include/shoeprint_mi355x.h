@@ -68,11 +68,15 @@ enum spr_ncc_method {
                          spr_ncc_plan_create returns SPR_ERR_WORKSPACE if that allocation fails */
   SPR_NCC_DIRECT = 2, /* sliding-window correlation in LDS (any shape that fits LDS) */
   SPR_NCC_FFT_POW2 = 3, /* as SPR_NCC_FFT but restricted to power-of-two grids (A/B and fallback for the 3*2^k grids) */
-  SPR_NCC_MFMA = 4    /* sliding-window correlation as a [queries x taps] x [taps x positions] product on the bf16 / f16 matrix
+  SPR_NCC_MFMA = 4,   /* sliding-window correlation as a [queries x taps] x [taps x positions] product on the bf16 / f16 matrix
                          cores: bfloat16 or float16 storage, cropped search maps up to 28 x 12 and cropped templates up to
                          30 x 16 (ResNet50 layer3 / VGG16 conv5_3 / EfficientNet stride-16 maps of a 512 x 256 image and their
                          scaled / rotated query variants; 28 x 12 on both sides has its own tuned instance);
                          SPR_ERR_UNSUPPORTED for anything else */
+  SPR_NCC_MFMA_F32 = 5 /* the same product for FLOAT32 storage, within float32 accuracy: both maps are centred in float32 and
+                         split into two bfloat16 numbers each (hi + lo), three bf16 matrix-core products per step
+                         (hi*hi + hi*lo + lo*hi, f32 accumulation); same shape bounds as SPR_NCC_MFMA, SPR_ERR_UNSUPPORTED for
+                         other storage types or shapes.  Chosen by name only: SPR_NCC_AUTO never resolves to it */
 };
 
 typedef void* spr_stream_t;
@@ -100,7 +104,7 @@ typedef struct spr_ncc_shape {
 
 int spr_ncc_plan_create(const spr_ncc_shape* shape, spr_ncc_plan** plan_out);
 void spr_ncc_plan_destroy(spr_ncc_plan* plan);
-/* The method the plan resolved SPR_NCC_AUTO to (SPR_NCC_FFT / SPR_NCC_DIRECT / SPR_NCC_MFMA). */
+/* The method the plan resolved to: SPR_NCC_FFT / SPR_NCC_DIRECT / SPR_NCC_MFMA for SPR_NCC_AUTO, or SPR_NCC_MFMA_F32. */
 int spr_ncc_plan_method(const spr_ncc_plan* plan);
 /* FFT grid the plan uses ({0,0} for the direct method): rows, cols. */
 int spr_ncc_plan_fft_size(const spr_ncc_plan* plan, int32_t* rows, int32_t* cols);

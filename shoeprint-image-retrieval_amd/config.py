@@ -44,6 +44,7 @@ class Mi355xConfig(TypedDict, total=False):
     dtype: str
     ncc_method: str
     max_prepared_gib: float
+    f32_matrix_cores: bool  # with ncc_method "auto": float32 plans the "mfma_f32" method covers run on the bf16 matrix cores
     weights: str
     gallery_cache: str  # directory for persisted gallery features (feature_cache.py); "" = off
     extractor_dtype: str  # "float32" (the reference's arithmetic) | "bfloat16" | "float16": compute type of the extractor
@@ -57,7 +58,7 @@ class Config(TypedDict, total=False):
 
 
 MI355X_DEFAULTS: dict[str, Any] = {"dtype": "float32", "ncc_method": "auto", "max_prepared_gib": 0.0, "weights": "",
-                                   "gallery_cache": "", "extractor_dtype": "float32"}
+                                   "gallery_cache": "", "extractor_dtype": "float32", "f32_matrix_cores": False}
 
 
 def normalise(raw: dict) -> Config:

@@ -46,7 +46,7 @@ int64_t pair_tiles_per_launch(int pairs_per_tile, int threads) {
 
 size_t prepared_query_item_bytes(const NccGeom& g, int method) {
   size_t b;
-  if (method == SPR_NCC_MFMA) return mfma_query_item_bytes(g);
+  if (method == SPR_NCC_MFMA || method == SPR_NCC_MFMA_F32) return mfma_query_item_bytes(g);
   if (method == SPR_NCC_FFT)
     b = sizeof(cf) * static_cast<size_t>(g.channels) * g.spec_per_chan + static_cast<size_t>(g.channels);  // + dead flags
   else
@@ -56,7 +56,7 @@ size_t prepared_query_item_bytes(const NccGeom& g, int method) {
 
 size_t prepared_gallery_item_bytes(const NccGeom& g, int method) {
   size_t b;
-  if (method == SPR_NCC_MFMA) return mfma_gallery_item_bytes(g);
+  if (method == SPR_NCC_MFMA || method == SPR_NCC_MFMA_F32) return mfma_gallery_item_bytes(g);
   if (method == SPR_NCC_FFT)
     b = static_cast<size_t>(g.channels) * (sizeof(cf) * g.spec_per_chan + sizeof(float) * g.inv_per_chan) +
         static_cast<size_t>(g.channels);  // + one dead flag per channel
@@ -69,7 +69,7 @@ size_t prepared_gallery_item_bytes(const NccGeom& g, int method) {
 
 struct spr_ncc_plan {
   spr::NccGeom geom;
-  int method;              // resolved: SPR_NCC_FFT, SPR_NCC_DIRECT or SPR_NCC_MFMA
+  int method;              // resolved: SPR_NCC_FFT, SPR_NCC_DIRECT, SPR_NCC_MFMA or SPR_NCC_MFMA_F32
   spr::PlanScratch scratch{};
   // A plan that owns device scratch its kernels write (mfma_x, team_sync, ws) orders its own calls: every scoring call
   // records `done` behind its launches, and a call that arrives on ANOTHER stream waits for it first - two streams sharing a
@@ -142,7 +142,7 @@ extern "C" int spr_ncc_plan_create(const spr_ncc_shape* shape, spr_ncc_plan** pl
     return SPR_ERR_ARG;
   }
   if (shape->method != SPR_NCC_AUTO && shape->method != SPR_NCC_FFT && shape->method != SPR_NCC_DIRECT &&
-      shape->method != SPR_NCC_FFT_POW2 && shape->method != SPR_NCC_MFMA) {
+      shape->method != SPR_NCC_FFT_POW2 && shape->method != SPR_NCC_MFMA && shape->method != SPR_NCC_MFMA_F32) {
     set_error("spr_ncc_plan_create: unknown method %d", shape->method);
     return SPR_ERR_ARG;
   }
@@ -166,6 +166,10 @@ extern "C" int spr_ncc_plan_create(const spr_ncc_shape* shape, spr_ncc_plan** pl
   if (shape->method == SPR_NCC_MFMA) {
     if (!mfma_ok) { set_error("matrix-core method: bfloat16 / float16 maps of 28x12 (cropped) on both sides only, got dtype %d, query %dx%d vs gallery %dx%d", g.dtype, g.th, g.tw, g.ih, g.iw); return SPR_ERR_UNSUPPORTED; }
     method = SPR_NCC_MFMA;
+  } else if (shape->method == SPR_NCC_MFMA_F32) {  // asked for by name only: SPR_NCC_AUTO never resolves to it
+    gm = g;
+    if (!mfma_f32_geometry(gm)) { set_error("float32 matrix-core method: float32 maps, cropped search maps up to 28x12 and cropped templates up to 30x16 only, got dtype %d, query %dx%d vs gallery %dx%d", g.dtype, g.th, g.tw, g.ih, g.iw); return SPR_ERR_UNSUPPORTED; }
+    method = SPR_NCC_MFMA_F32;
   } else if (shape->method == SPR_NCC_AUTO && mfma_auto) {
     method = SPR_NCC_MFMA;
   } else if (shape->method == SPR_NCC_FFT || shape->method == SPR_NCC_FFT_POW2) {
@@ -185,7 +189,7 @@ extern "C" int spr_ncc_plan_create(const spr_ncc_shape* shape, spr_ncc_plan** pl
   spr_ncc_plan* p = new (std::nothrow) spr_ncc_plan();
   if (!p) { set_error("out of host memory"); return SPR_ERR_ARG; }
   p->method = method;
-  p->geom = method == SPR_NCC_FFT ? gf : method == SPR_NCC_MFMA ? gm : gd;
+  p->geom = method == SPR_NCC_FFT ? gf : (method == SPR_NCC_MFMA || method == SPR_NCC_MFMA_F32) ? gm : gd;
   PlanScratch& sc = p->scratch;
   if (method == SPR_NCC_MFMA && mfma_workspace_bytes(p->geom) > 0 &&
       hipMalloc(reinterpret_cast<void**>(&sc.mfma_x), mfma_workspace_bytes(p->geom)) != hipSuccess) {
@@ -264,7 +268,7 @@ static int prepare(spr_ncc_plan* plan, bool is_query, const void* maps, int64_t 
   if (!maps || !prepared) { set_error("%s: null pointer", who); return SPR_ERR_ARG; }
   const PrepCall c{is_query, maps, n, prepared, static_cast<hipStream_t>(stream)};
   if (plan->method == SPR_NCC_FFT) return launch_prep_fft(plan->geom, plan->scratch, c);
-  if (plan->method == SPR_NCC_MFMA) return launch_prep_mfma(plan->geom, plan->scratch, c);
+  if (plan->method == SPR_NCC_MFMA || plan->method == SPR_NCC_MFMA_F32) return launch_prep_mfma(plan->geom, plan->scratch, c);
   return launch_prep_direct(plan->geom, plan->scratch, c);
 }
 
@@ -283,7 +287,7 @@ static int score_pairs(spr_ncc_plan* plan, const PairCall& c) {
   if (rc != SPR_OK) return rc;
   if (plan->method == SPR_NCC_FFT)
     rc = launch_pair_fft(plan->geom, plan->scratch, c);
-  else if (plan->method == SPR_NCC_MFMA)
+  else if (plan->method == SPR_NCC_MFMA || plan->method == SPR_NCC_MFMA_F32)
     rc = launch_pair_mfma(plan->geom, plan->scratch, c);
   else
     rc = launch_pair_direct(plan->geom, plan->scratch, c);

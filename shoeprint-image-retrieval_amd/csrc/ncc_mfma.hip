@@ -12,6 +12,11 @@
 //       corr_mfma_kernel (f32 matrix cores, 0.6 % of the flops) writes it before the pair kernel subtracts it at the end.
 //   split (SPR_NCC_MFMA_EXACT=0): B = I0z = hi + lo, two bfloat16 numbers (16 significant bits), two MFMAs per tile step,
 //       num = R - mean(t) * S1[p]  (S1 = window sum of I0z, :59); self-contained, half as fast.
+//   float32 maps (SPR_NCC_MFMA_F32): BOTH operands centred in float32 and split, t0 = t_hi + t_lo and I0z = I_hi + I_lo, and
+//       num = sum t_hi I_hi + t_hi I_lo + t_lo I_hi - mean(t_hi + t_lo) * S1[p]: three MFMAs per tile step (the fourth
+//       product is of order 2^-32), nothing raw enters a product, so neither the correction matrix nor the exact shift.
+//       Every channel takes TWO periods of the schedule below - t_hi x (I_hi, I_lo), then t_lo x I_hi onto the same
+//       accumulators - and is weighted once, after the second.
 // B is never materialised: it is a Toeplitz gather from the zero-padded map of the channel, kept in LDS in eight copies
 // shifted by one element each so that every lane's eight consecutive taps are one aligned ds_read_b128.
 // A fragment (8 taps of 16 positions) depends on (row of the position + row of the tap) only, so one fragment read
@@ -202,10 +207,13 @@ struct MPrepSizes {
 //                                                          inside the map at position p, SI = window sum of the raw map
 // The last term is a weight of the pair kernel's epilogue like before (b * SI in place of b * S1); the middle one is a
 // contraction over the channels per position, X[q,g,p] = sum_c (a St0)[q,c,p] * (b mean(I))[g,c,p], left to corr_mfma_kernel.
-template <class M, bool EXACT, bool FIXED>
+// F32 (float32 maps, never EXACT): the query side writes the centred template as two planes of bfloat16 rows (hi, then lo)
+// and {a, a * mean(hi + lo)} (mean_term = 0: {a, 0}, an A/B switch); the gallery side is the split form's as it stands.
+template <class M, bool EXACT, bool FIXED, bool F32 = false>
 __global__ void __launch_bounds__(kThreads)
 prep_mfma_kernel(NccGeom g, int is_query, const void* __restrict__ maps, unsigned char* __restrict__ prepared,
-                 size_t item_bytes) {
+                 size_t item_bytes, int mean_term) {
+  static_assert(!(F32 && EXACT), "float32 maps: the hi + lo form only");
   // Real sizes (cropped): template th x tw inside the FH x 16 frame, search map ih x iw inside the TH x TW frame.  FIXED (the
   // equal-size instance: template = map = the frame of positions): compile-time constants - with run-time sizes the kernel took
   // 51 ms instead of 31 for BASELINE config 3's gallery.
@@ -256,6 +264,24 @@ prep_mfma_kernel(NccGeom g, int is_query, const void* __restrict__ maps, unsigne
     float mean;
     load_centred(maps, base, g.q_w, g.crop, th, tw, g.dtype, x0, red, &mean);
     const float scale = template_scale(x0, th * tw, red);
+    if constexpr (F32) {
+      uint16_t* rows = reinterpret_cast<uint16_t*>(out_item + static_cast<size_t>(c) * (2 * M::kQMapBytes));
+      double s = 0.0;  // sum of hi + lo: not exactly zero
+      for (int i = tid; i < M::FH * 16; i += wg_size()) {
+        const int u = (i >> 4) - fy, v = (i & 15) - fx;
+        const unsigned w = hilo_word((u >= 0 && u < th && v >= 0 && v < tw) ? x0[u * tw + v] : 0.0f);
+        rows[i] = static_cast<uint16_t>(w >> 16);
+        rows[M::FH * 16 + i] = static_cast<uint16_t>(w & 0xffffu);
+        s += static_cast<double>(bf16_value(w >> 16)) + static_cast<double>(bf16_value(w & 0xffffu));
+      }
+      const float resid = mean_term ? static_cast<float>(block_sum(s, red) / static_cast<double>(th * tw)) : 0.0f;
+      float* sc = reinterpret_cast<float*>(out_item + static_cast<size_t>(g.channels) * (2 * M::kQMapBytes));
+      if (tid == 0) {
+        sc[2 * c] = scale;
+        sc[2 * c + 1] = scale * resid;
+      }
+      return;
+    }
     const float kappa = exact_shift(base, g.q_w, th, tw, mean);
     // the template frame in the storage type (taps as stored, or shifted by kappa; zero outside the template)
     uint16_t* rows = reinterpret_cast<uint16_t*>(out_item + static_cast<size_t>(c) * M::kQMapBytes);
@@ -337,7 +363,7 @@ prep_mfma_kernel(NccGeom g, int is_query, const void* __restrict__ maps, unsigne
 //     sums are differences of INCLUSIVE prefixes picked at run-time positions: the prefixes go through LDS (a register array
 //     cannot be indexed at run time without scratch) - along the row (written and read back by the same lane), then down
 //     the columns.
-template <class M, bool EXACT>
+template <class M, bool EXACT, bool F32 = false>
 __global__ void __launch_bounds__(64)
 prep_gallery_wave_kernel(NccGeom g, const void* __restrict__ maps, unsigned char* __restrict__ prepared, size_t item_bytes) {
   constexpr int H = M::TH, W = M::TW;
@@ -352,16 +378,28 @@ prep_gallery_wave_kernel(NccGeom g, const void* __restrict__ maps, unsigned char
   const bool in_map = row < ih && chan_ok;    // this lane holds a row of the map
   const bool frame_row = row < H && chan_ok;  // every row of the frame is written (zeros outside the map)
   const int cc = chan_ok ? c : g.channels - 1, rr = row < ih ? row : ih - 1;
-  const uint16_t* raw = static_cast<const uint16_t*>(maps) +
-                        ((item * g.channels + cc) * static_cast<size_t>(g.g_h) + (rr + g.crop)) * g.g_w + g.crop;
+  static_assert(!(F32 && EXACT), "float32 maps: the hi + lo form only");
+  const size_t row_at = ((item * g.channels + cc) * static_cast<size_t>(g.g_h) + (rr + g.crop)) * g.g_w + g.crop;
   unsigned bits[W];
-#pragma unroll
-  for (int k = 0; k < W; ++k) bits[k] = raw[k < iw ? k : iw - 1];
   float v[W];
+  if constexpr (F32) {
+    const float* raw = static_cast<const float*>(maps) + row_at;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      bits[k] = 0u;
+      v[k] = raw[k < iw ? k : iw - 1];
+    }
+  } else {
+    const uint16_t* raw = static_cast<const uint16_t*>(maps) + row_at;
+#pragma unroll
+    for (int k = 0; k < W; ++k) bits[k] = raw[k < iw ? k : iw - 1];
+#pragma unroll
+    for (int k = 0; k < W; ++k) v[k] = from_storage(bits[k], g.dtype);
+  }
   double s = 0.0;
 #pragma unroll
   for (int k = 0; k < W; ++k) {
-    v[k] = in_map && k < iw ? from_storage(bits[k], g.dtype) : 0.0f;
+    v[k] = in_map && k < iw ? v[k] : 0.0f;
     s += static_cast<double>(v[k]);
   }
 #pragma unroll
@@ -580,7 +618,11 @@ corr_mfma_kernel(int channels, int nq_here, int ng, const unsigned char* __restr
 }
 
 // ---- pair kernel: grid = (gallery items, blocks of 64 queries) ---------------------------------------------------------
-template <class M, bool MAPS, bool EXACT, bool F16>
+// F32 (float32 maps; hi + lo on both sides, so neither EXACT nor F16): the prepared query holds two planes of template rows
+// per channel, and the schedule below runs over 2 * channels PASSES - pass 2c: t_hi of channel c against both planes of its
+// image, pass 2c + 1: t_lo against the hi plane, continuing the same accumulators.  "Channel" in the comments of the schedule
+// then reads "pass"; the parity PAR of a period is the pass kind.  Only tiles that finish a lo pass are weighted.
+template <class M, bool MAPS, bool EXACT, bool F16, bool F32 = false>
 __global__ void __launch_bounds__(kThreads, 1)
 pair_mfma_kernel(MfmaArgs g, const unsigned char* __restrict__ pq, const unsigned char* __restrict__ pg,
                  float* __restrict__ scores, float* __restrict__ maps_out) {
@@ -589,6 +631,8 @@ pair_mfma_kernel(MfmaArgs g, const unsigned char* __restrict__ pq, const unsigne
   const int lane = tid & 63, wave = tid >> 6, col = lane & 15, kg = lane >> 4;
   const size_t gi = blockIdx.x;
   const int q0 = static_cast<int>(blockIdx.y) * 64;
+  static_assert(!F32 || (!EXACT && !F16), "float32 maps: bfloat16 hi + lo, no correction matrix");
+  constexpr int kQChan = (F32 ? 2 : 1) * M::kQMapBytes;  // template rows of one channel
   const int nq_here = g.nq - q0 < 64 ? g.nq - q0 : 64;
   const bool active = wave * 16 < nq_here;  // a wave without queries still stages the channel images
 
@@ -650,7 +694,7 @@ pair_mfma_kernel(MfmaArgs g, const unsigned char* __restrict__ pq, const unsigne
 #pragma unroll
   for (int r = 0; r < 4; ++r)
     sc_off[r] = static_cast<unsigned>(clampq(wave * 16 + 4 * kg + r)) * g.q_item_bytes +
-                static_cast<unsigned>(g.channels) * M::kQMapBytes;
+                static_cast<unsigned>(g.channels) * kQChan;
   auto load_a = [&](int c, int ks) { return buf_ld16v(q_rs, a_off, static_cast<unsigned>(c) * M::kQMapBytes + ks * 64); };
 
   // fragment read addresses: tile phase ph covers positions 16*ph + col (+ 16*TP per tile group)
@@ -662,6 +706,13 @@ pair_mfma_kernel(MfmaArgs g, const unsigned char* __restrict__ pq, const unsigne
     frag_base[ph] = k * 16 + (m0 >> 3) * M::JS + (y + (kg >> 1)) * M::RS;
   }
 
+  // spr_ncc_maps: row and column of this lane's position in the first tile of a phase (tile group tg: DY * tg rows further down)
+  int map_py[M::TP], map_px[M::TP];
+#pragma unroll
+  for (int ph = 0; ph < M::TP; ++ph) {
+    map_py[ph] = (16 * ph + col) / M::TW;
+    map_px[ph] = 16 * ph + col - map_py[ph] * M::TW;
+  }
   auto mfma = [](u32x4 a, u32x4 b, f32x4 c) {
     if constexpr (F16) return mfma_f16_16x16x32(a, b, c);
     else return mfma_bf16_16x16x32(a, b, c);
@@ -680,6 +731,7 @@ pair_mfma_kernel(MfmaArgs g, const unsigned char* __restrict__ pq, const unsigne
   for (int t = 0; t < M::NTILE; ++t) { run[t] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
   u32x4 A[2][M::KS];
   const int last_c = g.channels - 1;
+  const int passes = F32 ? 2 * g.channels : g.channels, last_p = passes - 1;  // periods of the schedule (+ 1 to drain)
   if (active) {
 #pragma unroll
     for (int ks = 0; ks < M::KS; ++ks) {
@@ -688,7 +740,7 @@ pair_mfma_kernel(MfmaArgs g, const unsigned char* __restrict__ pq, const unsigne
     }
     // (the first PERIOD - DY * (NTG - 1) offsets of a channel are done with before the previous period ends)
 #pragma unroll
-    for (int ks = 0; ks < (M::PERIOD - M::DY * (M::NTG - 1)) / 2; ++ks) A[1][ks] = load_a(last_c < 1 ? last_c : 1, ks);
+    for (int ks = 0; ks < (M::PERIOD - M::DY * (M::NTG - 1)) / 2; ++ks) A[1][ks] = load_a(last_p < 1 ? last_p : 1, ks);
   }
   stage_load(0);
   __syncthreads();  // the zero fill is complete
@@ -708,12 +760,20 @@ pair_mfma_kernel(MfmaArgs g, const unsigned char* __restrict__ pq, const unsigne
   auto period = [&](auto par_c, int c) {
     constexpr int PAR = decltype(par_c)::value;
     unsigned char* buf_cur = lds + b_cur;
-    unsigned char* buf_prev = lds + b_prev;
+    // F32: both passes of a channel read ONE image - the lo pass has it as current and as previous, stages nothing, and the
+    // buffers rotate (and the workgroup meets) once per channel, behind the lo pass
+    constexpr bool kLoPass = F32 && PAR == 1, kHiPass = F32 && PAR == 0;
+    unsigned char* buf_prev = lds + (kLoPass ? b_cur : b_prev);
     unsigned char* buf_next = lds + b_next;
-    const int c1 = c + 1 < g.channels ? c + 1 : last_c, c2 = c + 2 < g.channels ? c + 2 : last_c;
+    const int chan = F32 ? c >> 1 : c;  // the channel of pass c
+    const int c1 = c + 1 < passes ? c + 1 : last_p, c2 = chan + 2 < g.channels ? chan + 2 : last_c;
     if (active) {
+      if constexpr (kLoPass) {  // {a, a * mean} of this channel: due when its first tiles finish, at the end of this period
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
+        for (int r = 0; r < 4; ++r) sc_ld[r] = buf_ld8(q_rs, sc_off[r], static_cast<unsigned>(chan) * 8u);
+      }
+#pragma unroll
+      for (int r = 0; r < (F32 ? 0 : 4); ++r) {
         // (the loaded pair is first needed by the last steps of the period: its zeroing for the extra period waits until
         // mid-period - done here, the select made every period start with a full memory latency in front of its first MFMA)
         sc_prev[r] = sc_cur[r];
@@ -741,20 +801,21 @@ pair_mfma_kernel(MfmaArgs g, const unsigned char* __restrict__ pq, const unsigne
       auto epilogue = [&](int t, bool of_prev, int chan) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const f32x2 w = of_prev ? sc_prev[r] : sc_cur[r];
+          const f32x2 w = of_prev && !F32 ? sc_prev[r] : sc_cur[r];  // (F32: one channel's tiles at a time are weighted)
           const float v = ebv * acc[t][r];
-          run[t][r] = fmaf(-w.y, ebsv, fmaf(w.x, v, run[t][r]));
+          // (spr_ncc_maps passes no score matrix: the F32 instance of it keeps no channel sums - 84 registers it has no room for)
+          if constexpr (!(F32 && MAPS)) run[t][r] = fmaf(-w.y, ebsv, fmaf(w.x, v, run[t][r]));
           if constexpr (MAPS) {  // spr_ncc_maps: the channel's own map of the first query
             if (r == 0 && wave == 0 && kg == 0 && chan >= 0 && chan < g.channels) {
               float m = fmaf(-w.y, ebsv, w.x * v);
               if constexpr (EXACT) {  // this channel's term of the contraction, for the one pair of spr_ncc_maps
                 const int cp = pad16(g.channels), pos = 16 * t + col;
-                const float* U = reinterpret_cast<const float*>(q_block + static_cast<size_t>(g.channels) * (M::kQMapBytes + 8));
+                const float* U = reinterpret_cast<const float*>(q_block + static_cast<size_t>(g.channels) * (kQChan + 8));
                 const float* V = g_item.V();
                 m -= U[static_cast<size_t>(pos) * cp + chan] * V[static_cast<size_t>(pos) * cp + chan];
               }
-              const int py = (16 * t + col) / M::TW, px = (16 * t + col) - py * M::TW;
-              if (py < g.ih && px < g.iw) maps_out[(static_cast<size_t>(chan) * g.ih + py) * g.iw + px] = m;
+              const int py = M::DY * (t / M::TP) + map_py[t % M::TP], px = map_px[t % M::TP];
+              if (py < g.ih && px < g.iw) maps_out[(chan * g.ih + py) * g.iw + px] = m;
             }
           }
         }
@@ -768,11 +829,11 @@ pair_mfma_kernel(MfmaArgs g, const unsigned char* __restrict__ pq, const unsigne
         constexpr int sg = 2 * (j / M::TP), ph = j % M::TP, slot = j % kRing;
         if constexpr (!M::frag_zero(ph, sg)) {
           fch[slot] = load_frag(buf_cur, ph, sg, 0);
-          if constexpr (!EXACT) fcl[slot] = load_frag(buf_cur, ph, sg, 1);
+          if constexpr (!EXACT && !kLoPass) fcl[slot] = load_frag(buf_cur, ph, sg, 1);
         }
         if constexpr (sg + M::PERIOD <= M::SMAX && !M::frag_zero(ph, sg + M::PERIOD)) {
           fph[slot] = load_frag(buf_prev, ph, sg + M::PERIOD, 0);
-          if constexpr (!EXACT) fpl[slot] = load_frag(buf_prev, ph, sg + M::PERIOD, 1);
+          if constexpr (!EXACT && !kHiPass) fpl[slot] = load_frag(buf_prev, ph, sg + M::PERIOD, 1);  // (the previous pass is a lo pass)
         }
       };
       static_for<0, kAhead>(issue);
@@ -787,7 +848,9 @@ pair_mfma_kernel(MfmaArgs g, const unsigned char* __restrict__ pq, const unsigne
         (void)eb_now; (void)ebs_now;
         constexpr int tnext = finished(it);
         float nb = 0.f, nbs = 0.f;
-        if constexpr (tnext >= 0) {
+        // F32: a tile of the current pass is weighted if that is a lo pass, one of the previous pass if this is a hi pass
+        constexpr bool weigh_next = !F32 || (tnext < M::TP ? kLoPass : kHiPass);
+        if constexpr (tnext >= 0 && weigh_next) {
           const f32x2 w = (tnext < M::TP ? eb_cur : eb_prev)[16 * tnext + col];
           nb = w.x;
           nbs = w.y;
@@ -796,15 +859,19 @@ pair_mfma_kernel(MfmaArgs g, const unsigned char* __restrict__ pq, const unsigne
         if constexpr (tdone >= 0 && SPR_MFMA_ABL != 1) {
           // (group 0's last tile is finished by the last step of the PREVIOUS period: by now it belongs to channel c - 1)
           constexpr bool cur_chan = tdone < M::TP && it != 0;
-          epilogue(tdone, !cur_chan, cur_chan ? c : c - 1);
+          if constexpr (!F32) epilogue(tdone, !cur_chan, cur_chan ? c : c - 1);
+          else if constexpr (cur_chan ? kLoPass : kHiPass) epilogue(tdone, false, cur_chan ? chan : chan - 1);
         }
-        if constexpr (tnext >= 0) { ebv = nb; ebsv = nbs; }
+        if constexpr (tnext >= 0 && weigh_next) { ebv = nb; ebsv = nbs; }
         if constexpr (it == NIT / 2) {
           static_assert(NIT / 2 < NIT - M::TP, "the current channel's weights are first used by the last sigma step");
 #pragma unroll
-          for (int r = 0; r < 4; ++r) sc_cur[r] = c < g.channels ? sc_ld[r] : f32x2{0.f, 0.f};
+          for (int r = 0; r < 4; ++r) {
+            if constexpr (!F32) sc_cur[r] = c < g.channels ? sc_ld[r] : f32x2{0.f, 0.f};
+            else if constexpr (kLoPass) sc_cur[r] = sc_ld[r];  // (the tiles the previous channel had left are all weighted by now)
+          }
         }
-        if constexpr (SPR_MFMA_ABL != 3 && it >= IT_STAGE && it < IT_STAGE + 8 * kStageEvery && (it - IT_STAGE) % kStageEvery == 0) {
+        if constexpr (SPR_MFMA_ABL != 3 && !kLoPass && it >= IT_STAGE && it < IT_STAGE + 8 * kStageEvery && (it - IT_STAGE) % kStageEvery == 0) {
           stage_store_part(buf_next, std::integral_constant<int, (it - IT_STAGE) / kStageEvery>{});
           if constexpr (it == IT_STAGE + 7 * kStageEvery) stage_load(c2);
         }
@@ -816,16 +883,16 @@ pair_mfma_kernel(MfmaArgs g, const unsigned char* __restrict__ pq, const unsigne
             constexpr int ks = d / 2;
             static_assert(M::first_ks(tg, ph) * 2 + M::DY * tg < M::PERIOD, "a tile starts in its own channel's period");
             if constexpr (!M::frag_zero(ph, sg)) {
-              if constexpr (ks == M::first_ks(tg, ph))
+              if constexpr (ks == M::first_ks(tg, ph) && !kLoPass)
                 acc[t] = mfma(A[PAR][ks], fch[slot], f32x4{0.f, 0.f, 0.f, 0.f});
               else
                 acc[t] = mfma(A[PAR][ks], fch[slot], acc[t]);
-              if constexpr (!EXACT) acc[t] = mfma(A[PAR][ks], fcl[slot], acc[t]);
+              if constexpr (!EXACT && !kLoPass) acc[t] = mfma(A[PAR][ks], fcl[slot], acc[t]);
             }
           } else if constexpr (!M::frag_zero(ph, sg + M::PERIOD)) {
             constexpr int ks = (d + M::PERIOD) / 2;
             acc[t] = mfma(A[PAR ^ 1][ks], fph[slot], acc[t]);
-            if constexpr (!EXACT) acc[t] = mfma(A[PAR ^ 1][ks], fpl[slot], acc[t]);
+            if constexpr (!EXACT && !kHiPass) acc[t] = mfma(A[PAR ^ 1][ks], fpl[slot], acc[t]);
           }
         });
         // template row pairs nobody needs any more: the previous channel's (the slowest group has just used it) is
@@ -854,21 +921,23 @@ pair_mfma_kernel(MfmaArgs g, const unsigned char* __restrict__ pq, const unsigne
 #endif
         sched_fence();
       });
-    } else {
+    } else if constexpr (!kLoPass) {
       stage_store(buf_next);
       stage_load(c2);
     }
-    if (SPR_MFMA_ABL != 5) __syncthreads();  // channel c + 1 is staged; nobody reads channel c - 1's image any more
-    const int t0 = b_prev;
-    b_prev = b_cur; b_cur = b_next; b_next = t0;
+    if constexpr (!kHiPass) {
+      if (SPR_MFMA_ABL != 5) __syncthreads();  // channel c + 1 is staged; nobody reads channel c - 1's image any more
+      const int t0 = b_prev;
+      b_prev = b_cur; b_cur = b_next; b_next = t0;
+    }
   };
-  for (int c = 0; c <= g.channels; c += 2) {
+  for (int c = 0; c <= passes; c += 2) {
     period(std::integral_constant<int, 0>{}, c);
-    if (c + 1 <= g.channels) period(std::integral_constant<int, 1>{}, c + 1);
+    if (c + 1 <= passes) period(std::integral_constant<int, 1>{}, c + 1);
   }
   // group 0's last tile of the last period is still to be weighted - with weight 0 (it belongs to "channel" channels)
 
-  if (!active || !scores) return;  // spr_ncc_maps passes no score matrix
+  if (!active || !scores || (F32 && MAPS)) return;  // spr_ncc_maps passes no score matrix
   // spatial maximum per query: over this lane's tiles, then over the sixteen lanes holding the other positions
   if constexpr (EXACT) {
 #pragma unroll
@@ -907,12 +976,12 @@ static_assert(MGEN::kMaxTh == 30 && MGEN::kMaxTw == 16, "general instance");
 bool mfma_tuned_shape(const NccGeom& g) {
   return g.th == M2812::TH && g.tw == M2812::TW && g.ih == M2812::TH && g.iw == M2812::TW;
 }
-bool mfma_shape_ok(const NccGeom& g) {
-  if (g.dtype != SPR_BF16 && g.dtype != SPR_F16) return false;
+bool mfma_frame_ok(const NccGeom& g) {  // the sizes either instance covers, whatever the storage type
   if (mfma_tuned_shape(g)) return true;
   return g.th >= 1 && g.tw >= 1 && g.ih >= 1 && g.iw >= 1 && g.th <= MGEN::kMaxTh && g.tw <= MGEN::kMaxTw && g.ih <= MGEN::TH &&
          g.iw <= MGEN::TW;
 }
+bool mfma_shape_ok(const NccGeom& g) { return (g.dtype == SPR_BF16 || g.dtype == SPR_F16) && mfma_frame_ok(g); }
 
 // the instance of a plan: f(M2812{}) or f(MGEN{})
 template <class F>
@@ -933,9 +1002,19 @@ bool mfma_geometry(NccGeom& g) {
   return mfma_query_item_bytes(g) * 64 < (static_cast<size_t>(1) << 31);
 }
 
+// SPR_NCC_MFMA_F32: float32 maps of the same sizes, both operands as hi + lo
+bool mfma_f32_geometry(NccGeom& g) {
+  if (g.dtype != SPR_F32 || !mfma_frame_ok(g)) return false;
+  g.mfma_general = mfma_tuned_shape(g) ? 0 : 1;
+  g.mfma_exact = 0;
+  g.mfma_f32 = 1;
+  return mfma_query_item_bytes(g) * 64 < (static_cast<size_t>(1) << 31);
+}
+
 size_t mfma_query_item_bytes(const NccGeom& g) {
   return with_instance(g, [&](auto m) {
     using M = decltype(m);
+    if (g.mfma_f32) return align_up(static_cast<size_t>(g.channels) * (2 * M::kQMapBytes + 8), 256);  // rows of t_hi, of t_lo; {a, a * mean}
     size_t b = static_cast<size_t>(g.channels) * (M::kQMapBytes + 8);
     if (g.mfma_exact) b += sizeof(float) * M::NPOS * static_cast<size_t>(pad16(g.channels));
     return align_up(b, 256);
@@ -960,6 +1039,17 @@ static int launch_prep_mfma_m(const NccGeom& g, const PlanScratch&, const PrepCa
   const unsigned n = static_cast<unsigned>(c.n);
   constexpr bool kFixed = MPrepSizes<M>::kFixed;  // (the equal-size instance is only chosen for template = map = frame)
   int rc;
+  if (g.mfma_f32) {  // float32 maps: the same two routes for the galleries, the table kernel for the queries
+    if (!c.is_query && env_int("SPR_MFMA_PREP", 1) != 0) {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(prep_gallery_wave_kernel<M, false, true>), dim3((g.channels + 1) / 2, n), dim3(64), 0,
+                         c.stream, g, c.maps, prepared, item_bytes);
+      return check_launch("prep_gallery_wave_kernel");
+    }
+    // SPR_MFMA_F32_MEAN=0: without the mean(t_hi + t_lo) * S1 term of the epilogue (an A/B switch)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(prep_mfma_kernel<M, false, kFixed, true>), dim3(g.channels, n), dim3(64), lds, c.stream, g,
+                       c.is_query ? 1 : 0, c.maps, prepared, item_bytes, env_int("SPR_MFMA_F32_MEAN", 1) != 0 ? 1 : 0);
+    return check_launch("prep_mfma_kernel");
+  }
   if (!c.is_query && env_int("SPR_MFMA_PREP", 1) != 0) {  // (SPR_MFMA_PREP=0: the galleries too go through the kernel of the queries, an A/B switch)
     auto wave = g.mfma_exact ? prep_gallery_wave_kernel<M, true> : prep_gallery_wave_kernel<M, false>;  // two channels per wave, no tables
     hipLaunchKernelGGL(wave, dim3((g.channels + 1) / 2, n), dim3(64), 0, c.stream, g, c.maps, prepared, item_bytes);
@@ -967,7 +1057,7 @@ static int launch_prep_mfma_m(const NccGeom& g, const PlanScratch&, const PrepCa
   } else {
     auto kernel = g.mfma_exact ? prep_mfma_kernel<M, true, kFixed> : prep_mfma_kernel<M, false, kFixed>;
     // one wave per (item, channel): maps of 336 pixels leave a 256-lane workgroup waiting at its ~20 barriers
-    hipLaunchKernelGGL(kernel, dim3(g.channels, n), dim3(64), lds, c.stream, g, c.is_query ? 1 : 0, c.maps, prepared, item_bytes);
+    hipLaunchKernelGGL(kernel, dim3(g.channels, n), dim3(64), lds, c.stream, g, c.is_query ? 1 : 0, c.maps, prepared, item_bytes, 0);
     rc = check_launch("prep_mfma_kernel");
   }
   if (rc == SPR_OK && g.mfma_exact && !c.is_query) {
@@ -983,9 +1073,9 @@ int launch_prep_mfma(const NccGeom& g, const PlanScratch& s, const PrepCall& c) 
   return with_instance(g, [&](auto m) { return launch_prep_mfma_m<decltype(m)>(g, s, c); });
 }
 
-template <class M, bool EXACT, bool F16>
+template <class M, bool EXACT, bool F16, bool F32 = false>
 static int launch_pair_mfma_t(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
-  auto kernel = c.maps_out ? pair_mfma_kernel<M, true, EXACT, F16> : pair_mfma_kernel<M, false, EXACT, F16>;
+  auto kernel = c.maps_out ? pair_mfma_kernel<M, true, EXACT, F16, F32> : pair_mfma_kernel<M, false, EXACT, F16, F32>;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
   const size_t q_item = mfma_query_item_bytes(g), g_item = mfma_gallery_item_bytes(g);
   const unsigned char* pqb = static_cast<const unsigned char*>(c.pq);
@@ -1039,6 +1129,7 @@ int launch_pair_mfma(const NccGeom& g, const PlanScratch& s, const PairCall& c) 
   if (c.nq == 0 || c.ng == 0) return SPR_OK;
   return with_instance(g, [&](auto m) {
     using M = decltype(m);
+    if (g.mfma_f32) return launch_pair_mfma_t<M, false, false, true>(g, s, c);
     if (g.dtype == SPR_F16) return launch_pair_mfma_t<M, true, true>(g, s, c);
     return g.mfma_exact ? launch_pair_mfma_t<M, true, false>(g, s, c) : launch_pair_mfma_t<M, false, false>(g, s, c);
   });

@@ -58,6 +58,7 @@ struct NccGeom {
   // matrix-core method only -----------------------------------------------------------------
   int mfma_exact;      // 1: raw search map on the matrix cores + correction matrix (ncc_mfma.hip), 0: hi + lo
   int mfma_general;    // 1: the general instance (template up to 30 x 16 on a map up to 28 x 12), 0: the 28 x 12 / 28 x 12 one
+  int mfma_f32;        // 1: SPR_NCC_MFMA_F32 - float32 maps, both operands centred and split into hi + lo (never with mfma_exact)
 };
 
 constexpr int kStrip = 8;  // output pixels per register strip in the direct kernel
@@ -96,7 +97,7 @@ int launch_pair_direct(const NccGeom& g, const PlanScratch& s, const PairCall& c
 int launch_prep_fft(const NccGeom& g, const PlanScratch& s, const PrepCall& c);
 int launch_pair_fft(const NccGeom& g, const PlanScratch& s, const PairCall& c);
 int launch_pair6(const NccGeom& g, const PlanScratch& s, const PairCall& c);  // six-wave pair kernel (ncc_pair6.hip)
-int launch_prep_mfma(const NccGeom& g, const PlanScratch& s, const PrepCall& c);  // bf16 / f16 matrix cores (ncc_mfma.hip)
+int launch_prep_mfma(const NccGeom& g, const PlanScratch& s, const PrepCall& c);  // bf16 / f16 matrix cores (ncc_mfma.hip), both methods
 int launch_pair_mfma(const NccGeom& g, const PlanScratch& s, const PairCall& c);
 // Pair kernels run one workgroup per pair in tiles of `pairs_per_tile`; HIP refuses a grid of 2^32 work-items or
 // more, so a launch takes at most this many tiles (SPR_NCC_MAX_TILES lowers it: tests of the slicing).
@@ -107,6 +108,7 @@ int pair6_max_rows();  // cropped search-map rows / columns the six-wave kernel 
 int pair6_max_cols();
 size_t fft_workspace_bytes(const NccGeom& g);  // what a plan with this geometry must allocate (0: none)
 bool mfma_geometry(NccGeom& g);  // true if an instantiated kernel covers this plan (fills mfma_exact)
+bool mfma_f32_geometry(NccGeom& g);  // the same for SPR_NCC_MFMA_F32 (float32 maps)
 size_t mfma_query_item_bytes(const NccGeom& g);
 size_t mfma_gallery_item_bytes(const NccGeom& g);
 size_t mfma_workspace_bytes(const NccGeom& g);  // the plan's correction matrix of the exact form (0: none)

@@ -69,7 +69,8 @@ int method_code(const std::string& m) {
   if (m == "direct") return SPR_NCC_DIRECT;
   if (m == "fft_pow2") return SPR_NCC_FFT_POW2;
   if (m == "mfma") return SPR_NCC_MFMA;
-  TORCH_CHECK(false, "unknown NCC method '", m, "' (auto | fft | direct | fft_pow2 | mfma)");
+  if (m == "mfma_f32") return SPR_NCC_MFMA_F32;
+  TORCH_CHECK(false, "unknown NCC method '", m, "' (auto | fft | direct | fft_pow2 | mfma | mfma_f32)");
   return -1;
 }
 

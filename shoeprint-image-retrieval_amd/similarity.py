@@ -27,7 +27,8 @@ from . import _lib
 from ._lib import NCC_AUTO, NCC_DIRECT, NCC_FFT, NccShape
 
 CROP = 2  # similarity.py:92-93
-_METHODS = {"auto": NCC_AUTO, "fft": NCC_FFT, "direct": NCC_DIRECT, "fft_pow2": _lib.NCC_FFT_POW2, "mfma": _lib.NCC_MFMA}
+_METHODS = {"auto": NCC_AUTO, "fft": NCC_FFT, "direct": NCC_DIRECT, "fft_pow2": _lib.NCC_FFT_POW2, "mfma": _lib.NCC_MFMA,
+            "mfma_f32": _lib.NCC_MFMA_F32}
 _DTYPES = {np.dtype(np.float32): _lib.F32, np.dtype(np.float16): _lib.F16}
 
 
@@ -89,15 +90,19 @@ class NccScorer:
     ----------
     device : backend object (default ``TorchDevice()``: PyTorch-ROCm on the current GPU)
     library: ``_lib.Library`` (default: the in-tree libshoeprint_mi355x.so)
-    method : "auto" | "fft" | "direct" | "fft_pow2" | "mfma"  (pair-kernel choice, see the C header)
+    method : "auto" | "fft" | "direct" | "fft_pow2" | "mfma" | "mfma_f32"  (pair-kernel choice, see the C header)
     max_prepared_bytes: HBM budget for the prepared form of one gallery chunk (default: a third
         of the free memory, at most 64 GiB); larger galleries are processed chunk by chunk.
     storage: HBM storage type of feature batches uploaded from host lists ("float32" | "float16" | "bfloat16");
         arithmetic is float32 / float64 whatever the storage.
+    f32_matrix_cores: with method "auto", a float32 plan first asks for "mfma_f32" (float32 maps as hi + lo on the bf16
+        matrix cores: cropped maps up to 28 x 12, cropped templates up to 30 x 16) and takes what "auto" gives where that
+        method does not cover the plan - per plan, so ragged sets and query variants mix methods by shape.
     """
 
     def __init__(self, device=None, library: _lib.Library | None = None, method: str = "auto",
-                 max_prepared_bytes: int | None = None, crop: int = CROP, storage: str = "float32"):
+                 max_prepared_bytes: int | None = None, crop: int = CROP, storage: str = "float32",
+                 f32_matrix_cores: bool = False):
         self.lib = library or _lib.load_library()
         if device is None:
             from .device import TorchDevice
@@ -110,6 +115,7 @@ class NccScorer:
         if storage not in ("float32", "float16", "bfloat16"):
             raise ValueError(f"unknown storage type {storage!r}")
         self.storage = storage
+        self.f32_matrix_cores = bool(f32_matrix_cores)
         self._plans: dict[tuple, _Plan] = {}
         self._variants = None
 
@@ -120,7 +126,14 @@ class NccScorer:
         key = (channels, tuple(q_hw), tuple(g_hw), dkey, crop, self.method)
         p = self._plans.get(key)
         if p is None:
-            p = _Plan(self.lib, channels, q_hw, g_hw, crop, code, self.method)
+            if self.f32_matrix_cores and self.method == NCC_AUTO and code == _lib.F32:
+                try:
+                    p = _Plan(self.lib, channels, q_hw, g_hw, crop, code, _lib.NCC_MFMA_F32)
+                except _lib.SprError as e:
+                    if e.code != _lib.SPR_ERR_UNSUPPORTED:
+                        raise
+            if p is None:
+                p = _Plan(self.lib, channels, q_hw, g_hw, crop, code, self.method)
             self._plans[key] = p
         return p
 
@@ -175,7 +188,11 @@ class NccScorer:
             # north_star's named mechanism: the registered PyTorch-ROCm custom op (csrc/torch_ops.cpp), same entry points
             if str(q_dev.dtype) != str(g_dev.dtype):
                 raise ValueError(f"storage type mismatch: queries {q_dev.dtype}, gallery {g_dev.dtype}")
-            return self._torch_ops().ncc_scores(q_dev, g_dev, self.crop, _lib.METHOD_NAMES[self.method], self._budget())
+            method = self.method
+            if self.f32_matrix_cores:  # the op resolves a method name by itself: hand it the one this scorer's plan took
+                if self.plan(c, (qh, qw), (gh, gw), dtype=q_dev.dtype).method == _lib.NCC_MFMA_F32:
+                    method = _lib.NCC_MFMA_F32
+            return self._torch_ops().ncc_scores(q_dev, g_dev, self.crop, _lib.METHOD_NAMES[method], self._budget())
         if plan is None:
             if str(q_dev.dtype) != str(g_dev.dtype):
                 raise ValueError(f"storage type mismatch: queries {q_dev.dtype}, gallery {g_dev.dtype}")
@@ -355,21 +372,23 @@ _config_scorers: dict[tuple, NccScorer] = {}
 
 
 def scorer_from_config(config: dict, *, device=None, library: _lib.Library | None = None) -> NccScorer:
-    """The scorer that ``[mi355x]`` of run.toml asks for: ``ncc_method`` ("auto" | "fft" | "fft_pow2" | "direct" | "mfma"),
-    ``dtype`` (HBM storage type of the feature maps: "float32" | "float16" | "bfloat16") and ``max_prepared_gib`` (HBM
-    budget of one prepared gallery chunk; 0 = automatic).  Reference files, which have no such table, get the defaults."""
+    """The scorer that ``[mi355x]`` of run.toml asks for: ``ncc_method`` ("auto" | "fft" | "fft_pow2" | "direct" | "mfma" |
+    "mfma_f32"), ``dtype`` (HBM storage type of the feature maps: "float32" | "float16" | "bfloat16"), ``max_prepared_gib``
+    (HBM budget of one prepared gallery chunk; 0 = automatic) and ``f32_matrix_cores`` (see NccScorer).  Reference files,
+    which have no such table, get the defaults."""
     extra = config.get("mi355x") or {}
     method = extra.get("ncc_method", "auto") or "auto"
     storage = extra.get("dtype", "float32") or "float32"
     gib = float(extra.get("max_prepared_gib", 0.0) or 0.0)
     if method not in _METHODS:
         raise ValueError(f"[mi355x].ncc_method = {method!r}: expected one of {sorted(_METHODS)}")
-    key = (method, storage, gib, id(device), id(library))
-    if key == ("auto", "float32", 0.0, id(None), id(None)):
+    f32_mc = bool(extra.get("f32_matrix_cores", False))
+    key = (method, storage, gib, f32_mc, id(device), id(library))
+    if key == ("auto", "float32", 0.0, False, id(None), id(None)):
         return default_scorer()
     if key not in _config_scorers:
         _config_scorers[key] = NccScorer(device=device, library=library, method=method, storage=storage,
-                                         max_prepared_bytes=int(gib * (1 << 30)) if gib > 0 else None)
+                                         f32_matrix_cores=f32_mc, max_prepared_bytes=int(gib * (1 << 30)) if gib > 0 else None)
     return _config_scorers[key]
 
 
