@@ -364,6 +364,18 @@ int spr_effnet_forward_trace(spr_effnet_plan* plan, const uint8_t* images, int64
  * images / mean3 / inv_std3 / out as for spr_vgg16_forward. */
 typedef struct spr_densenet_plan spr_densenet_plan;
 int spr_densenet_plan_create(int32_t block, spr_densenet_plan** plan_out);
+/* With a compute type (as spr_effnet_plan_create_ex): SPR_F32 is spr_densenet_plan_create's plan; SPR_F16 / SPR_BF16, for
+ * block in [5, 12] (a plan that ends inside the stem must be f32: SPR_ERR_UNSUPPORTED), run every convolution on
+ * v_mfma_f32_16x16x32 with every tensor between layers stored in that type; the pre-activation scales / shifts, the biases,
+ * the accumulation, the average pool's sum and the closing BatchNorm stay f32 (the list of rounding points: densenet.hip).
+ * The caller then packs, at the offsets spr_densenet_op_info reports (floats) and with the sizes of that plan:
+ *   stem        w as 16-bit [k / 8][64][8], k = tap * 3 + plane, zero for k in [147, 160) (norm0 folded), b f32 [64]
+ *   dense 1x1   s, t f32 [cin]; w as 16-bit [2][ceil(cin / 64)][64][64] (second BatchNorm folded, zero behind cin), b f32 [128]
+ *   dense 3x3   w as 16-bit [1][9 * 2][32][64], K index = tap * 128 + c; b f32 [32] zeros
+ *   transition  s, t f32 [cin]; w as 16-bit [cout / 64][cin / 64][64][64], b f32 [cout] zeros
+ *   closing     s, t f32 [C] */
+int spr_densenet_plan_create_ex(int32_t block, int32_t compute, spr_densenet_plan** plan_out);
+int spr_densenet_plan_compute(const spr_densenet_plan* plan);
 void spr_densenet_plan_destroy(spr_densenet_plan* plan);
 int spr_densenet_num_ops(const spr_densenet_plan* plan);
 int spr_densenet_op_info(const spr_densenet_plan* plan, int32_t i, int32_t* info12);
@@ -374,6 +386,16 @@ size_t spr_densenet_workspace_bytes(const spr_densenet_plan* plan, int64_t n, in
 int spr_densenet_forward(spr_densenet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
                          int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
                          float* out, spr_stream_t stream);
+/* Per-layer trace of a 16-bit plan (see spr_resnet_forward_trace).  Records, all 16-bit NHWC but the last: the stem's output;
+ * block 1's tensor behind the max pool (its first 64 channels are written, the rest is whatever the workspace held); per
+ * dense layer its 128-channel intermediate; per dense block its complete tensor behind the last layer (slices are never
+ * overwritten: it holds every 3x3 result and every later layer's input); per transition its convolution's result and the
+ * next tensor behind the average pool (its first cout channels are written); the float32 NCHW output. */
+int spr_densenet_trace_layout(const spr_densenet_plan* plan, int64_t n, int32_t in_h, int32_t in_w, int64_t* records,
+                              size_t* total_bytes);
+int spr_densenet_forward_trace(spr_densenet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                               int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
+                               float* out, void* trace, spr_stream_t stream);
 
 /* ------------------------------------------------------------------ synthetic data
  * Bench/test support: the device twin of shoeprint_image_retrieval_amd/synth.py (bit-identical

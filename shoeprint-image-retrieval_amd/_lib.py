@@ -82,6 +82,8 @@ SIGNATURES = {
     "spr_vgg16_forward_taps": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                          _VP, _VP, _VP, _I32, C.POINTER(_I32), C.POINTER(_VP), _VP]),
     "spr_densenet_plan_create": (C.c_int, [_I32, C.POINTER(_VP)]),
+    "spr_densenet_plan_create_ex": (C.c_int, [_I32, _I32, C.POINTER(_VP)]),
+    "spr_densenet_plan_compute": (C.c_int, [_VP]),
     "spr_densenet_plan_destroy": (None, [_VP]),
     "spr_densenet_num_ops": (C.c_int, [_VP]),
     "spr_densenet_op_info": (C.c_int, [_VP, _I32, C.POINTER(_I32)]),
@@ -90,6 +92,9 @@ SIGNATURES = {
     "spr_densenet_workspace_bytes": (_SZ, [_VP, _I64, _I32, _I32]),
     "spr_densenet_forward": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                        _VP, _VP, _VP, _VP]),
+    "spr_densenet_trace_layout": (C.c_int, [_VP, _I64, _I32, _I32, C.POINTER(_I64), C.POINTER(_SZ)]),
+    "spr_densenet_forward_trace": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                             _VP, _VP, _VP, _VP, _VP]),
     "spr_effnet_plan_create": (C.c_int, [_I32, _I32, C.POINTER(_VP)]),
     "spr_effnet_plan_create_ex": (C.c_int, [_I32, _I32, _I32, C.POINTER(_VP)]),
     "spr_effnet_plan_compute": (C.c_int, [_VP]),

@@ -25,9 +25,9 @@ int launch_stem(const uint8_t* images, int64_t n, int in_h, int in_w, int in_cha
 int launch_stem16(int kind, int ks, int stride, const uint8_t* images, int64_t n, int in_h, int in_w, int in_channels,
                   const float* mean3, const float* inv_std3, const uint16_t* w16, const float* bias, int act, uint16_t* out,
                   hipStream_t s);
-// 3x3 / stride 2 / pad 1 max pool of an NHWC tensor [n][h][w][c] (ldo: channel stride of the f32 output)
+// 3x3 / stride 2 / pad 1 max pool of an NHWC tensor [n][h][w][c] (ldo: channel stride of the output; 16-bit: a multiple of 8)
 int launch_maxpool3(const float* in, int64_t n, int h, int w, int c, float* out, int ldo, hipStream_t s);
-int launch_maxpool3_16(const uint16_t* in, int64_t n, int h, int w, int c, uint16_t* out, hipStream_t s);
+int launch_maxpool3_16(const uint16_t* in, int64_t n, int h, int w, int c, uint16_t* out, int ldo, hipStream_t s);
 // implicit-GEMM convolution on the f32 matrix cores: (ks, stride) in (1, 1), (1, 2), (3, 1), (3, 2); see conv_gemm_kernel
 int launch_conv_gemm(int ks, int stride, const float* in, int64_t n, int h, int w, int cin, int cout, const float* wts,
                      const float* bias, const float* res, int act, int nchw, float* out, const float* in_scale, int cout_real,

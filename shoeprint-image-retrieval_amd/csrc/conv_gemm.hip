@@ -274,10 +274,11 @@ rpack16_kernel(const float* __restrict__ w, const float* __restrict__ b, float* 
 }
 
 // 3x3 / stride 2 / pad 1 max pool of the stem's (rounded, post-ReLU: non-negative) 16-bit NHWC output into the 16-bit NHWC
-// tensor layer1 reads: eight channels (16 bytes) per work-item; non-negative float16 / bfloat16 values order like their bit
-// patterns, so the maximum is taken on the 16-bit integers
+// tensor layer1 reads (channel stride ldo >= C, a multiple of 8: DenseNet's first block tensor is wider than the pool):
+// eight channels (16 bytes) per work-item; non-negative float16 / bfloat16 values order like their bit patterns, so the
+// maximum is taken on the 16-bit integers
 __global__ void __launch_bounds__(kThreads)
-maxpool3_16_kernel(const uint16_t* __restrict__ in, int H, int W, int C, uint16_t* __restrict__ out, size_t total8) {
+maxpool3_16_kernel(const uint16_t* __restrict__ in, int H, int W, int C, uint16_t* __restrict__ out, size_t total8, int ldo) {
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2, c8 = C / 8;
   for (size_t i = static_cast<size_t>(blockIdx.x) * kThreads + threadIdx.x; i < total8;
        i += static_cast<size_t>(gridDim.x) * kThreads) {
@@ -301,7 +302,7 @@ maxpool3_16_kernel(const uint16_t* __restrict__ in, int H, int W, int C, uint16_
     u32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = m[2 * e] | (m[2 * e + 1] << 16);
-    *reinterpret_cast<u32x4*>(out + i * 8) = o;
+    *reinterpret_cast<u32x4*>(out + (i / c8) * ldo + c) = o;
   }
 }
 
@@ -714,9 +715,9 @@ int launch_maxpool3(const float* in, int64_t n, int h, int w, int c, float* out,
   return check_launch("maxpool3_kernel");
 }
 
-int launch_maxpool3_16(const uint16_t* in, int64_t n, int h, int w, int c, uint16_t* out, hipStream_t s) {
+int launch_maxpool3_16(const uint16_t* in, int64_t n, int h, int w, int c, uint16_t* out, int ldo, hipStream_t s) {
   const size_t total8 = static_cast<size_t>(n) * out_size(h, 3, 2) * out_size(w, 3, 2) * c / 8;
-  hipLaunchKernelGGL(maxpool3_16_kernel, blocks_of(total8), dim3(kThreads), 0, s, in, h, w, c, out, total8);
+  hipLaunchKernelGGL(maxpool3_16_kernel, blocks_of(total8), dim3(kThreads), 0, s, in, h, w, c, out, total8, ldo);
   return check_launch("maxpool3_16_kernel");
 }
 

@@ -289,7 +289,7 @@ static int resnet_forward(spr_resnet_plan* plan, const uint8_t* images, int64_t 
     const int hp = (h + 1) / 2, wp = (w + 1) / 2;
     // (16-bit plans: the stem stored its activation rounded to the 16-bit type; the pooled tensor is layer1's operand)
     rc = f32 ? launch_maxpool3(buf[1], n, h, w, 64, buf[0], 64, s)
-             : launch_maxpool3_16(reinterpret_cast<const uint16_t*>(buf[1]), n, h, w, 64, b16[0], s);
+             : launch_maxpool3_16(reinterpret_cast<const uint16_t*>(buf[1]), n, h, w, 64, b16[0], 64, s);
     if (rc == SPR_OK) rc = trace_copy(trace, &lay, 1, b16[0], s);
     if (rc != SPR_OK) return rc;
     h = hp; w = wp;

@@ -150,13 +150,13 @@ def _fold_bn(w, b, gamma, beta, mu, var, eps):
     return w * scale[:, None, None, None], (b - mu) * scale + beta
 
 
-def _gemm_layout(w, cout_p: int, cin_p: int, kc: int) -> np.ndarray:
-    """[cout][cin][k][k] -> [cout_p / 64][K / kc][64][kc], zero-padded, K index = tap * cin_p + c: kc = 16 is
-    conv_gemm_kernel's layout, kc = 64 conv_gemm16_kernel's."""
+def _gemm_layout(w, cout_p: int, cin_p: int, kc: int, bn: int = 64) -> np.ndarray:
+    """[cout][cin][k][k] -> [cout_p / bn][K / kc][bn][kc], zero-padded, K index = tap * cin_p + c: kc = 16 is
+    conv_gemm_kernel's layout, kc = 64 conv_gemm16_kernel's and (bn = 64 | 32) dnet_gemm16_kernel's."""
     cout, cin, k, _ = w.shape
     wp = np.zeros((cout_p, k * k, cin_p), np.float32)
     wp[:cout, :, :cin] = w.reshape(cout, cin, k * k).transpose(0, 2, 1)
-    return np.ascontiguousarray(wp.reshape(cout_p // 64, 64, k * k * cin_p // kc, kc).transpose(0, 2, 1, 3)).ravel()
+    return np.ascontiguousarray(wp.reshape(cout_p // bn, bn, k * k * cin_p // kc, kc).transpose(0, 2, 1, 3)).ravel()
 
 
 def _padded(a, n: int) -> np.ndarray:
@@ -334,10 +334,13 @@ class _EffNet(_Family):
 
 class _DenseNet(_Family):
     """Layers: ``Model.densenet_ops``; parameters per layer in torchvision's module order (synth.densenet_parameters)."""
-    prefix, count, lister, seeder, half = "densenet", "num_ops", "densenet_ops", synth.densenet_parameters, False
+    prefix, count, lister, seeder = "densenet", "num_ops", "densenet_ops", synth.densenet_parameters
 
     def create(self, m, handle):
-        return m.lib.spr_densenet_plan_create(m.block, handle)
+        if m.compute != "float32" and m.block < 5:
+            raise NotImplementedError("a 16-bit DenseNet plan needs a dense block behind the stem (block >= 5); "
+                                      "use [mi355x].extractor_dtype = \"float32\"")
+        return m.lib.spr_densenet_plan_create_ex(m.block, _COMPUTE[m.compute], handle)
 
     def names(self, m, layers):
         return densenet_state_names(layers)
@@ -356,6 +359,22 @@ class _DenseNet(_Family):
     def pack(self, m, ops, parameters):
         eps = np.float32(self.bn_eps)
         packed = np.zeros(m.lib.spr_densenet_packed_bytes(m.handle) // 4, np.float32)
+        packed16 = packed.view(np.uint16)  # 16-bit plans: the convolutions' weights as float16 / bfloat16 bit patterns
+        half = m.compute != "float32"
+        if half and m.block < 5:
+            raise NotImplementedError("a 16-bit DenseNet plan needs a dense block behind the stem (block >= 5)")
+
+        def bits16(a):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            return synth.bfloat16_bits(a) if m.compute == "bfloat16" else a.astype(np.float16).view(np.uint16)
+
+        def put_w(op, w, cout_p, bn=64):
+            """A GEMM convolution's weights: conv_gemm_kernel's f32 layout, or dnet_gemm16_kernel's rounded to 16 bits."""
+            if half:
+                wk = _gemm_layout(w, cout_p, -(-w.shape[1] // 64) * 64, 64, bn)
+                packed16[2 * op["w_off"]:2 * op["w_off"] + wk.size] = bits16(wk)
+            else:
+                put(op["w_off"], _gemm_layout(w, cout_p, w.shape[1], 16))
 
         def affine(gamma, beta, mu, var):  # eval-mode BatchNorm as x * s + t (in FRONT of a convolution: not folded)
             s = gamma / np.sqrt(var + eps)
@@ -374,7 +393,13 @@ class _DenseNet(_Family):
                 if op["flags"] & 1:
                     s, t = affine(*p[1:5])
                     w, b = w * s[:, None, None, None], t
-                put(op["w_off"], w.reshape(64, 3, 49).transpose(2, 1, 0))  # [tap][c][n]
+                if half:  # [k / 8][64][8], k = tap * 3 + plane, 147 real values of 160 (stem16_kernel)
+                    ws = np.zeros((160, 64), np.float32)
+                    ws[:147] = w.transpose(2, 3, 1, 0).reshape(147, 64)
+                    ws = ws.reshape(20, 8, 64).transpose(0, 2, 1)
+                    packed16[2 * op["w_off"]:2 * op["w_off"] + ws.size] = bits16(ws).ravel()
+                else:
+                    put(op["w_off"], w.reshape(64, 3, 49).transpose(2, 1, 0))  # [tap][c][n]
                 put(op["b_off"], b)
             elif op["kind"] == 1:
                 s1, t1 = affine(*p[0:4])
@@ -383,17 +408,17 @@ class _DenseNet(_Family):
                 if w.shape != (128, op["cin"], 1, 1):
                     raise ValueError(f"dense 1x1 parameter shape {w.shape} for {op['cin']} input channels")
                 put(op["s_off"], s1); put(op["t_off"], t1)
-                put(op["w_off"], _gemm_layout(w * s2[:, None, None, None], 128, op["cin"], 16)); put(op["b_off"], t2)
+                put_w(op, w * s2[:, None, None, None], 128); put(op["b_off"], t2)
             elif op["kind"] == 2:
                 if p[0].shape != (32, 128, 3, 3):
                     raise ValueError(f"dense 3x3 parameter shape {p[0].shape}")
-                put(op["w_off"], _gemm_layout(p[0], 64, 128, 16))
+                put_w(op, p[0], 32 if half else 64, 32 if half else 64)
             elif op["kind"] == 3:
                 s, t = affine(*p[0:4])
                 if p[4].shape != (op["cout"], op["cin"], 1, 1):
                     raise ValueError(f"transition parameter shape {p[4].shape}")
                 put(op["s_off"], s); put(op["t_off"], t)
-                put(op["w_off"], _gemm_layout(p[4], op["cout"], op["cin"], 16))
+                put_w(op, p[4], op["cout"])
             else:
                 s, t = affine(*p[0:4])
                 put(op["s_off"], s); put(op["t_off"], t)
@@ -438,8 +463,8 @@ class Model:
         if self.compute not in _COMPUTE:
             raise ValueError(f"[mi355x].extractor_dtype = {self.compute!r}: expected one of {sorted(_COMPUTE)}")
         if self.compute != "float32" and not fam.half:
-            raise NotImplementedError(f"{self.model_str}: the 16-bit matrix-core path is built for the VGG, ResNet50 and "
-                                      "EfficientNet extractors; use [mi355x].extractor_dtype = \"float32\"")
+            raise NotImplementedError(f"{self.model_str}: this backbone has no 16-bit matrix-core path; "
+                                      "use [mi355x].extractor_dtype = \"float32\"")
         handle = C.c_void_p()
         self.lib.check(fam.create(self, C.byref(handle)))
         self.handle = handle
