@@ -253,6 +253,22 @@ int spr_vgg16_forward_taps(spr_vgg16_plan* plan, const uint8_t* images, int64_t 
                            void* workspace, float* out, int32_t n_taps, const int32_t* tap_convs, float* const* tap_out,
                            spr_stream_t stream);
 
+/* Per-layer trace of a 16-bit plan, for tests (the record format and the contract are spr_resnet_trace_layout's and
+ * spr_resnet_forward_trace's, below): spr_vgg16_forward_trace is spr_vgg16_forward_taps - the same kernels, the same `out`,
+ * the same taps - that also copies, behind every stage and on the same stream, what that stage stored into `trace`.  One
+ * record per convolution of spr_vgg16_conv_shape's list, in that order:
+ *   record 0                 the first convolution's output (bias, ReLU): 16-bit NHWC [n][h][w][64]
+ *   record i, 0 < i < last   what stage i stored, behind bias / ReLU / the fused 2x2 max pool: 16-bit NHWC [n][h_i][w_i][cout_i]
+ *   the last record          the float32 NCHW output [n][C][h][w], i.e. `out`
+ * Refused with SPR_ERR_UNSUPPORTED by both entry points: float32 plans, and a 16-bit plan that consists of its first
+ * convolution alone (it runs in float32, see spr_vgg_plan_create_ex, and stores no 16-bit record). */
+int spr_vgg16_trace_layout(const spr_vgg16_plan* plan, int64_t n, int32_t in_h, int32_t in_w, int64_t* records,
+                           size_t* total_bytes);
+int spr_vgg16_forward_trace(spr_vgg16_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                            int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
+                            void* workspace, float* out, int32_t n_taps, const int32_t* tap_convs, float* const* tap_out,
+                            void* trace, spr_stream_t stream);
+
 /* ------------------------------------------------------------------ RGB route of CLAHE (network.py:199-204)
  * The reference equalises a colour image on its L channel: cv2.cvtColor(RGB2LAB) -> CLAHE(L) -> cv2.cvtColor(LAB2RGB).
  * 8-bit convention (L * 255/100, a + 128, b + 128; sRGB, D65); interleaved uint8 [n_pixels, 3] in and out.  `tables`:

@@ -81,6 +81,9 @@ SIGNATURES = {
                                     _VP, _VP, _VP, _VP]),
     "spr_vgg16_forward_taps": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                          _VP, _VP, _VP, _I32, C.POINTER(_I32), C.POINTER(_VP), _VP]),
+    "spr_vgg16_trace_layout": (C.c_int, [_VP, _I64, _I32, _I32, C.POINTER(_I64), C.POINTER(_SZ)]),
+    "spr_vgg16_forward_trace": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                          _VP, _VP, _VP, _I32, C.POINTER(_I32), C.POINTER(_VP), _VP, _VP]),
     "spr_densenet_plan_create": (C.c_int, [_I32, C.POINTER(_VP)]),
     "spr_densenet_plan_create_ex": (C.c_int, [_I32, _I32, C.POINTER(_VP)]),
     "spr_densenet_plan_compute": (C.c_int, [_VP]),

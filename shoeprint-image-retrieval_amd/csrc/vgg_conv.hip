@@ -720,10 +720,36 @@ extern "C" size_t spr_vgg16_workspace_bytes(const spr_vgg16_plan* plan, int64_t 
   return 2 * align_up(biggest * (plan->compute == SPR_F32 ? sizeof(float) : sizeof(uint16_t)), 256);
 }
 
+// Trace records of a 16-bit plan (spr_vgg16_trace_layout): what every stage stored, behind bias / ReLU / pool - 16-bit NHWC
+// for the stem and every stage but the last, the float32 NCHW output for the last.
+static TraceLayout vgg_trace_layout(const spr_vgg16_plan* plan, int64_t n, int in_h, int in_w) {
+  TraceLayout lay;
+  lay.n = n;
+  int h = in_h, w = in_w;
+  for (size_t i = 0; i < plan->stages.size(); ++i) {
+    const Stage& st = plan->stages[i];
+    if (st.pool) { h /= 2; w /= 2; }
+    if (i + 1 == plan->stages.size()) lay.add(h, w, st.cout, SPR_F32, 1);
+    else lay.add(h, w, st.cout, plan->compute, 0);
+  }
+  return lay;
+}
+
+// A 16-bit plan with stages behind its first convolution; anything else has no trace.
+static int vgg_trace_refusal(const spr_vgg16_plan* plan, const char* who) {
+  if (plan->compute == SPR_F32) { set_error("%s: 16-bit plans only", who); return SPR_ERR_UNSUPPORTED; }
+  if (plan->stages.size() < 2) {
+    set_error("%s: a plan that is its first convolution alone runs in float32 and stores no 16-bit record", who);
+    return SPR_ERR_UNSUPPORTED;
+  }
+  return SPR_OK;
+}
+
+// trace: null (the plain forward and the taps forward), or where every stage's stored result is copied (vgg_trace_layout)
 static int vgg_forward(spr_vgg16_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
                        int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
-                       float* out, int32_t n_taps, const int32_t* tap_convs, float* const* tap_out, spr_stream_t stream,
-                       const char* who) {
+                       float* out, int32_t n_taps, const int32_t* tap_convs, float* const* tap_out, unsigned char* trace,
+                       spr_stream_t stream, const char* who) {
   if (!plan) { set_error("%s: null plan", who); return SPR_ERR_ARG; }
   if (n < 0 || n > 65535 || in_h < 1 || in_w < 1 || (in_channels != 1 && in_channels != 3)) {
     set_error("%s: bad sizes (n in [0, 65535], in_channels 1 or 3)", who);
@@ -753,6 +779,8 @@ static int vgg_forward(spr_vgg16_plan* plan, const uint8_t* images, int64_t n, i
                             static_cast<int>(kConvLds));
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv16_kernel<kBF16>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             static_cast<int>(kConvLds));
+  TraceLayout lay;
+  if (trace) lay = vgg_trace_layout(plan, n, in_h, in_w);
   int h = in_h, w = in_w;
   const float* cur = nullptr;
   for (size_t i = 0; i < plan->stages.size(); ++i) {
@@ -793,6 +821,8 @@ static int vgg_forward(spr_vgg16_plan* plan, const uint8_t* images, int64_t n, i
       const int rc = check_launch("conv_mfma_kernel");
       if (rc != SPR_OK) return rc;
     }
+    const int rc = trace_copy(trace, &lay, i, dst, s);
+    if (rc != SPR_OK) return rc;
     if (st.pool) { h /= 2; w /= 2; }
     cur = dst;
   }
@@ -803,7 +833,7 @@ extern "C" int spr_vgg16_forward(spr_vgg16_plan* plan, const uint8_t* images, in
                                  int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
                                  void* workspace, float* out, spr_stream_t stream) {
   return vgg_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, 0, nullptr, nullptr,
-                     stream, "spr_vgg16_forward");
+                     nullptr, stream, "spr_vgg16_forward");
 }
 
 extern "C" int spr_vgg16_forward_taps(spr_vgg16_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
@@ -811,5 +841,27 @@ extern "C" int spr_vgg16_forward_taps(spr_vgg16_plan* plan, const uint8_t* image
                                       void* workspace, float* out, int32_t n_taps, const int32_t* tap_convs,
                                       float* const* tap_out, spr_stream_t stream) {
   return vgg_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, n_taps, tap_convs,
-                     tap_out, stream, "spr_vgg16_forward_taps");
+                     tap_out, nullptr, stream, "spr_vgg16_forward_taps");
+}
+
+extern "C" int spr_vgg16_trace_layout(const spr_vgg16_plan* plan, int64_t n, int32_t in_h, int32_t in_w, int64_t* records,
+                                      size_t* total_bytes) {
+  if (!plan || n < 0 || in_h < 1 || in_w < 1) { set_error("spr_vgg16_trace_layout: bad argument"); return SPR_ERR_ARG; }
+  const int refused = vgg_trace_refusal(plan, "spr_vgg16_trace_layout");
+  if (refused != SPR_OK) return refused;
+  int32_t c = 0, oh = 0, ow = 0;
+  const int rc = spr_vgg16_output_shape(plan, in_h, in_w, &c, &oh, &ow);  // SPR_ERR_SHAPE: the image vanishes under the pools
+  if (rc != SPR_OK) return rc;
+  return trace_query(vgg_trace_layout(plan, n, in_h, in_w), records, total_bytes);
+}
+
+extern "C" int spr_vgg16_forward_trace(spr_vgg16_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                                       int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
+                                       void* workspace, float* out, int32_t n_taps, const int32_t* tap_convs,
+                                       float* const* tap_out, void* trace, spr_stream_t stream) {
+  if (!plan || !trace) { set_error("spr_vgg16_forward_trace: null pointer"); return SPR_ERR_ARG; }
+  const int refused = vgg_trace_refusal(plan, "spr_vgg16_forward_trace");
+  if (refused != SPR_OK) return refused;
+  return vgg_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, n_taps, tap_convs,
+                     tap_out, static_cast<unsigned char*>(trace), stream, "spr_vgg16_forward_trace");
 }

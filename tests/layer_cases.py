@@ -116,6 +116,7 @@ class Trace:
     raw: list              # per record: uint16 [n][h][w][c] or float32 [n][c] / [n][c][h][w]
     out: np.ndarray        # the trace run's float32 output
     plain: np.ndarray      # the plain forward's output (same images)
+    taps: dict = field(default_factory=dict)  # plain VGG: conv index -> float32 [n][c][h][w] feature tap of the trace run
 
 
 def _images(n: int, hw) -> np.ndarray:
@@ -128,22 +129,20 @@ def _images(n: int, hw) -> np.ndarray:
     return np.stack([pool[i % len(pool)] for i in range(n)])
 
 
-def run_trace(m, lib, dev, imgs: np.ndarray) -> Trace:
-    """One spr_*_forward_trace of `m` (a 16-bit effnet / resnet network.Model) on imgs, with `out`, the workspace (exactly
-    spr_*_workspace_bytes) and the trace inside one allocation, each between poisoned bands that must stay untouched; the
-    interiors start as all-ones bytes (NaN in every float type), so anything left unwritten shows.  Also runs the plain
-    forward on the same images."""
-    kind = "effnet" if m.effnet else "resnet"
-    layout = getattr(lib, f"spr_{kind}_trace_layout")
-    n, h, w = imgs.shape
+def trace_records(layout, handle, n: int, h: int, w: int):
+    """(records, total bytes) of an spr_*_trace_layout: (offset, h, w, c, dtype, nchw) per record."""
     total = C.c_size_t(0)
-    cnt = layout(m.handle, n, h, w, None, C.byref(total))
+    cnt = layout(handle, n, h, w, None, C.byref(total))
     assert cnt > 0, cnt
     rec = (C.c_int64 * (6 * cnt))()
-    assert layout(m.handle, n, h, w, rec, C.byref(total)) == cnt
-    records = [tuple(int(v) for v in rec[6 * i: 6 * i + 6]) for i in range(cnt)]
-    c, oh, ow = m.output_shape(h, w)
-    sizes = [n * c * oh * ow * 4, getattr(lib, f"spr_{kind}_workspace_bytes")(m.handle, n, h, w), total.value]
+    assert layout(handle, n, h, w, rec, C.byref(total)) == cnt
+    return [tuple(int(v) for v in rec[6 * i: 6 * i + 6]) for i in range(cnt)], total.value
+
+
+def run_guarded(dev, sizes, launch) -> list:
+    """Buffers of `sizes` bytes inside one allocation, each 256-byte aligned between poisoned bands of GUARD bytes that must
+    stay untouched; the interiors start as all-ones bytes (NaN in every float type), so anything left unwritten shows.
+    launch(buffers) enqueues the work; returns the buffers' bytes behind it (host arrays)."""
     starts, at = [], GUARD
     for sz in sizes:
         starts.append(at)
@@ -154,12 +153,7 @@ def run_trace(m, lib, dev, imgs: np.ndarray) -> Trace:
     sl = [buf[shift + s0: shift + s0 + sz] for s0, sz in zip(starts, sizes)]
     for b in sl:
         b[:] = 0xFF
-    img_dev = dev.to_device(imgs)
-    mean = (C.c_float * 3)(*m.mean)
-    inv_std = (C.c_float * 3)(*[np.float32(1.0) / np.float32(s) for s in m.std])
-    fwd = getattr(lib, f"spr_{kind}_forward_trace")
-    lib.check(fwd(m.handle, dev.ptr(img_dev), n, h, w, 1, mean, inv_std, dev.ptr(m.packed), dev.ptr(sl[1]), dev.ptr(sl[0]),
-                  dev.ptr(sl[2]), dev.stream()))
+    launch(sl)
     dev.synchronize()
     back = np.asarray(dev.to_host(buf))
     bands = np.ones(len(host), bool)
@@ -167,8 +161,11 @@ def run_trace(m, lib, dev, imgs: np.ndarray) -> Trace:
         bands[shift + s0: shift + s0 + sz] = False
     bad = np.nonzero(bands & (back != host))[0]
     assert bad.size == 0, f"{bad.size} guard-band bytes overwritten, first at {bad[:8].tolist()} (buffers at {starts}, +{shift})"
-    out = back[shift + starts[0]: shift + starts[0] + sizes[0]].view(np.float32).reshape(n, c, oh, ow).copy()
-    tr = back[shift + starts[2]: shift + starts[2] + sizes[2]]
+    return [back[shift + s0: shift + s0 + sz] for s0, sz in zip(starts, sizes)]
+
+
+def raw_records(tr: np.ndarray, records, n: int) -> list:
+    """The trace buffer's bytes as one array per record."""
     raw = []
     for off, rh, rw, rc, dt, nchw in records:
         if dt == 0:
@@ -176,8 +173,29 @@ def run_trace(m, lib, dev, imgs: np.ndarray) -> Trace:
             raw.append(a.reshape(n, rc, rh, rw).copy() if nchw else a.reshape(n, rc).copy())
         else:
             raw.append(tr[off: off + 2 * n * rh * rw * rc].view(np.uint16).reshape(n, rh, rw, rc).copy())
+    return raw
+
+
+def run_trace(m, lib, dev, imgs: np.ndarray) -> Trace:
+    """One spr_*_forward_trace of `m` (a 16-bit effnet / resnet network.Model) on imgs, with `out`, the workspace (exactly
+    spr_*_workspace_bytes) and the trace inside one allocation, each between poisoned bands that must stay untouched; the
+    interiors start as all-ones bytes (NaN in every float type), so anything left unwritten shows.  Also runs the plain
+    forward on the same images."""
+    kind = "effnet" if m.effnet else "resnet"
+    n, h, w = imgs.shape
+    records, total = trace_records(getattr(lib, f"spr_{kind}_trace_layout"), m.handle, n, h, w)
+    c, oh, ow = m.output_shape(h, w)
+    sizes = [n * c * oh * ow * 4, getattr(lib, f"spr_{kind}_workspace_bytes")(m.handle, n, h, w), total]
+    img_dev = dev.to_device(imgs)
+    mean = (C.c_float * 3)(*m.mean)
+    inv_std = (C.c_float * 3)(*[np.float32(1.0) / np.float32(s) for s in m.std])
+    fwd = getattr(lib, f"spr_{kind}_forward_trace")
+    back = run_guarded(dev, sizes, lambda sl: lib.check(fwd(m.handle, dev.ptr(img_dev), n, h, w, 1, mean, inv_std,
+                                                            dev.ptr(m.packed), dev.ptr(sl[1]), dev.ptr(sl[0]), dev.ptr(sl[2]),
+                                                            dev.stream())))
+    out = back[0].view(np.float32).reshape(n, c, oh, ow).copy()
     plain = np.asarray(dev.to_host(m.extract_device(img_dev)))
-    return Trace(records, raw, out, plain)
+    return Trace(records, raw_records(back[2], records, n), out, plain)
 
 
 # ---------------------------------------------------------------------------------------------------- the checks
@@ -267,7 +285,8 @@ def _check_f32(res: LayerResult, got: np.ndarray, y: torch.Tensor, lo: torch.Ten
 
 def _normalised(imgs: np.ndarray, mean, std, compute: str):
     """The stem's operand in both forms, rounded: the oracle's (x - mean) / std and the kernel's (x - mean) * (1 / std)."""
-    x = torch.from_numpy(imgs.astype(np.float32) / np.float32(255.0))[:, None].repeat(1, 3, 1, 1)
+    x = torch.from_numpy(imgs.astype(np.float32) / np.float32(255.0))
+    x = x.permute(0, 3, 1, 2).contiguous() if imgs.ndim == 4 else x[:, None].repeat(1, 3, 1, 1)  # RGB [N,H,W,3] | grey [N,H,W]
     m = torch.tensor(mean, dtype=torch.float32)[None, :, None, None]
     s = torch.tensor(std, dtype=torch.float32)[None, :, None, None]
     inv = torch.tensor([np.float32(1.0) / np.float32(v) for v in std], dtype=torch.float32)[None, :, None, None]
