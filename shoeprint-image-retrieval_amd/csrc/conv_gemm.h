@@ -1,13 +1,46 @@
 // Internal declarations of the extractor side: the host launchers of the convolution kernels that the backbones share
 // (each kernel lives in one translation unit; other files reach it through its launcher) and the trace records of the
-// 16-bit ResNet / EfficientNet plans.  All launchers enqueue on the stream and return SPR_OK / SPR_ERR_HIP, or
-// SPR_ERR_UNSUPPORTED for a kernel size / stride / tile combination that is not instantiated.
+// 16-bit plans (ResNet, EfficientNet, DenseNet, plain VGG).  All launchers enqueue on the stream and return SPR_OK /
+// SPR_ERR_HIP, or SPR_ERR_UNSUPPORTED for a kernel size / stride / tile combination that is not instantiated.
 #pragma once
+#include <algorithm>
 #include <vector>
 
 #include "spr_common.h"
 
 namespace spr {
+
+// grid of a grid-stride kernel over `total` items
+inline dim3 blocks_of(size_t total) {
+  return dim3(static_cast<unsigned>(std::min<size_t>((total + kThreads - 1) / kThreads, 65535 * 16)));
+}
+
+// One convolution (pad = ks / 2), as every convolution launcher below takes it.  A plain convolution names its geometry,
+// in / wts / bias / out and its activation; everything else is optional.  Tensor pointers are untyped: float32 for
+// launch_conv_gemm, the plan's 16-bit type for the others (wts: as the matching pack_* function wrote them); the launcher
+// that owns the kernel casts them.  A launcher given a field that its kernel has no path for returns SPR_ERR_UNSUPPORTED.
+struct ConvCall {
+  int ks = 1, stride = 1;
+  int64_t n = 0;                    // images
+  int h = 0, w = 0;                 // input pixels
+  int cin = 0, cout = 0;            // channels the GEMM reads / computes (multiples of the kernel's tile)
+  int cout_real = 0;                // cout is padded: channels of the float32 NCHW result (launch_conv_gemm: of the NHWC
+                                    // result too); 0: all of them
+  int lda = 0, ldc = 0;             // channel strides of the NHWC input / output tensors; 0: cin / cout
+  int c_off = 0;                    // first channel of the NHWC output tensor that is written
+  const void* in = nullptr;         // NHWC [n][h][w][lda]
+  const void* wts = nullptr;
+  const float* bias = nullptr;
+  const void* res = nullptr;        // residual operand, NHWC like the output with cout channels
+  const float* in_scale = nullptr;  // [image][cin] factors on the input (squeeze-excitation)
+  const float* pre_s = nullptr;     // per input channel: max(x * pre_s + pre_t, 0) on the operand (BatchNorm + ReLU in
+  const float* pre_t = nullptr;     // front of the convolution)
+  int act = 0;                      // 0 none, 1 ReLU (behind the residual sum), 2 SiLU (in front of it)
+  void* out = nullptr;              // NHWC result ...
+  float* out_nchw = nullptr;        // ... or, if not null, the float32 NCHW result [n][cout_real][ho][wo] (last layer)
+  int in_stride() const { return lda ? lda : cin; }
+  int out_stride() const { return ldc ? ldc : cout; }
+};
 
 // ---- conv_gemm.hip.  ks / stride / kind (SPR_F16 | SPR_BF16) pick the template instance; act: 0 none, 1 ReLU, 2 SiLU.
 // parameter packing of one convolution into `packed` at w_off / b_off (floats): the f32 GEMM layout (stem != 0: the f32
@@ -29,20 +62,16 @@ int launch_stem16(int kind, int ks, int stride, const uint8_t* images, int64_t n
 int launch_maxpool3(const float* in, int64_t n, int h, int w, int c, float* out, int ldo, hipStream_t s);
 int launch_maxpool3_16(const uint16_t* in, int64_t n, int h, int w, int c, uint16_t* out, int ldo, hipStream_t s);
 // implicit-GEMM convolution on the f32 matrix cores: (ks, stride) in (1, 1), (1, 2), (3, 1), (3, 2); see conv_gemm_kernel
-int launch_conv_gemm(int ks, int stride, const float* in, int64_t n, int h, int w, int cin, int cout, const float* wts,
-                     const float* bias, const float* res, int act, int nchw, float* out, const float* in_scale, int cout_real,
-                     int lda, int ldc, int c_off, const float* pre_s, const float* pre_t, hipStream_t s);
-// ... on the 16-bit matrix cores: the same four (ks, stride); see conv_gemm16_kernel.  bn_switch: this call honours
-// SPR_GEMM16_BN=128 (128-channel tiles where cout allows; not built for 3x3 / stride 1)
-int launch_conv_gemm16(int kind, int ks, int stride, const uint16_t* in, int64_t n, int h, int w, int cin, int cout,
-                       const uint16_t* w16, const float* bias, const uint16_t* res, int act, uint16_t* out, float* out32,
-                       const float* in_scale, int cout_real, bool bn_switch, hipStream_t s);
+int launch_conv_gemm(const ConvCall& c, hipStream_t s);
+// ... on the 16-bit matrix cores: the same four (ks, stride); see conv_gemm16_kernel (no lda / ldc / c_off / pre_s; cout_real
+// counts for the NCHW result only).  bn_switch: this call honours SPR_GEMM16_BN=128 (128-channel tiles where cout allows;
+// not built for 3x3 / stride 1)
+int launch_conv_gemm16(int kind, const ConvCall& c, bool bn_switch, hipStream_t s);
 
-// ---- vgg_conv.hip: its 16-bit 3x3 / stride 1 convolution, shared with the ResNet plans (NHWC 16-bit in / out)
+// ---- vgg_conv.hip: its 16-bit 3x3 / stride 1 convolution, shared with the ResNet plans (bias and ReLU only)
 int pack_conv16_3x3(int kind, const float* w, const float* b, float* packed, size_t w_off, size_t b_off, int cin, int cout,
                     hipStream_t s);
-int launch_conv16_3x3(int kind, const uint16_t* in, int64_t n, int h, int w, int cin, int cout, const uint16_t* w16,
-                      const float* bias, int relu, uint16_t* out, hipStream_t s);
+int launch_conv16_3x3(int kind, const ConvCall& c, hipStream_t s);
 
 // The argument checks every spr_*_forward starts with (`name`: the entry point, for the message).  SPR_OK with n == 0
 // means there is nothing to do.

@@ -657,9 +657,6 @@ conv_gemm16_kernel(const uint16_t* __restrict__ in, int n_img, int H, int W, int
 // Each picks its kernel instance as a function pointer (all instances of a kernel share one signature); a combination that
 // is not instantiated is an error, never another instance.
 namespace {
-dim3 blocks_of(size_t total) {  // grid of a grid-stride kernel over `total` items
-  return dim3(static_cast<unsigned>(std::min<size_t>((total + kThreads - 1) / kThreads, 65535 * 16)));
-}
 int out_size(int in, int ks, int stride) { return (in + 2 * (ks / 2) - ks) / stride + 1; }  // pad = ks / 2
 }  // namespace
 
@@ -721,19 +718,19 @@ int launch_maxpool3_16(const uint16_t* in, int64_t n, int h, int w, int c, uint1
   return check_launch("maxpool3_16_kernel");
 }
 
-int launch_conv_gemm(int ks, int stride, const float* in, int64_t n, int h, int w, int cin, int cout, const float* wts,
-                     const float* bias, const float* res, int act, int nchw, float* out, const float* in_scale, int cout_real,
-                     int lda, int ldc, int c_off, const float* pre_s, const float* pre_t, hipStream_t s) {
-  auto kernel = ks == 1 && stride == 1   ? conv_gemm_kernel<1, 1>
-                : ks == 1 && stride == 2 ? conv_gemm_kernel<1, 2>
-                : ks == 3 && stride == 1 ? conv_gemm_kernel<3, 1>
-                : ks == 3 && stride == 2 ? conv_gemm_kernel<3, 2>
-                                         : nullptr;
-  if (!kernel) { set_error("launch_conv_gemm: no %d x %d / stride %d instance", ks, ks, stride); return SPR_ERR_UNSUPPORTED; }
-  const long long m = static_cast<long long>(n) * out_size(h, ks, stride) * out_size(w, ks, stride);
-  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((m + kGM - 1) / kGM), static_cast<unsigned>(cout / kGN)), dim3(kThreads),
-                     0, s, in, static_cast<int>(n), h, w, cin, cout, wts, bias, res, act, nchw, out, in_scale, cout_real, lda, ldc,
-                     c_off, pre_s, pre_t);
+int launch_conv_gemm(const ConvCall& c, hipStream_t s) {
+  auto kernel = c.ks == 1 && c.stride == 1   ? conv_gemm_kernel<1, 1>
+                : c.ks == 1 && c.stride == 2 ? conv_gemm_kernel<1, 2>
+                : c.ks == 3 && c.stride == 1 ? conv_gemm_kernel<3, 1>
+                : c.ks == 3 && c.stride == 2 ? conv_gemm_kernel<3, 2>
+                                             : nullptr;
+  if (!kernel) { set_error("launch_conv_gemm: no %d x %d / stride %d instance", c.ks, c.ks, c.stride); return SPR_ERR_UNSUPPORTED; }
+  const long long m = static_cast<long long>(c.n) * out_size(c.h, c.ks, c.stride) * out_size(c.w, c.ks, c.stride);
+  float* out = c.out_nchw ? c.out_nchw : static_cast<float*>(c.out);
+  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((m + kGM - 1) / kGM), static_cast<unsigned>(c.cout / kGN)), dim3(kThreads),
+                     0, s, static_cast<const float*>(c.in), static_cast<int>(c.n), c.h, c.w, c.cin, c.cout,
+                     static_cast<const float*>(c.wts), c.bias, static_cast<const float*>(c.res), c.act, c.out_nchw ? 1 : 0, out,
+                     c.in_scale, c.cout_real, c.in_stride(), c.out_stride(), c.c_off, c.pre_s, c.pre_t);
   return check_launch("conv_gemm_kernel");
 }
 
@@ -745,13 +742,16 @@ auto gemm16_kernel_of(int kind) {
 }
 }  // namespace
 
-int launch_conv_gemm16(int kind, int ks, int stride, const uint16_t* in, int64_t n, int h, int w, int cin, int cout,
-                       const uint16_t* w16, const float* bias, const uint16_t* res, int act, uint16_t* out, float* out32,
-                       const float* in_scale, int cout_real, bool bn_switch, hipStream_t s) {
+int launch_conv_gemm16(int kind, const ConvCall& c, bool bn_switch, hipStream_t s) {
+  if (c.in_stride() != c.cin || c.out_stride() != c.cout || c.c_off != 0 || c.pre_s || c.pre_t) {
+    set_error("launch_conv_gemm16: conv_gemm16_kernel has no channel strides, channel offset or operand BatchNorm");
+    return SPR_ERR_UNSUPPORTED;
+  }
   // 128-channel tiles only on request (SPR_GEMM16_BN=128; tests and A/B runs)
   static const int forced = [] { const char* v = std::getenv("SPR_GEMM16_BN"); return v && *v ? std::atoi(v) : 0; }();
   // (measured on ResNet50 through layer3, batch 32: 17.9 k images/s with 64-channel tiles throughout, 16.9 k with 128)
-  const bool wide = bn_switch && cout % 128 == 0 && forced == 128;
+  const bool wide = bn_switch && c.cout % 128 == 0 && forced == 128;
+  const int ks = c.ks, stride = c.stride;
   auto kernel = ks == 1 && stride == 1   ? (wide ? gemm16_kernel_of<1, 1, 128>(kind) : gemm16_kernel_of<1, 1, 64>(kind))
                 : ks == 1 && stride == 2 ? (wide ? gemm16_kernel_of<1, 2, 128>(kind) : gemm16_kernel_of<1, 2, 64>(kind))
                 : ks == 3 && stride == 2 ? (wide ? gemm16_kernel_of<3, 2, 128>(kind) : gemm16_kernel_of<3, 2, 64>(kind))
@@ -761,10 +761,11 @@ int launch_conv_gemm16(int kind, int ks, int stride, const uint16_t* in, int64_t
     set_error("launch_conv_gemm16: no %d x %d / stride %d instance with %d-channel tiles", ks, ks, stride, wide ? 128 : 64);
     return SPR_ERR_UNSUPPORTED;
   }
-  const long long m = static_cast<long long>(n) * out_size(h, ks, stride) * out_size(w, ks, stride);
-  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((m + kHM - 1) / kHM), static_cast<unsigned>(cout / (wide ? 128 : 64))),
-                     dim3(kThreads), 0, s, in, static_cast<int>(n), h, w, cin, cout, w16, bias, res, act, out, out32, in_scale,
-                     cout_real);
+  const long long m = static_cast<long long>(c.n) * out_size(c.h, ks, stride) * out_size(c.w, ks, stride);
+  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((m + kHM - 1) / kHM), static_cast<unsigned>(c.cout / (wide ? 128 : 64))),
+                     dim3(kThreads), 0, s, static_cast<const uint16_t*>(c.in), static_cast<int>(c.n), c.h, c.w, c.cin, c.cout,
+                     static_cast<const uint16_t*>(c.wts), c.bias, static_cast<const uint16_t*>(c.res), c.act,
+                     static_cast<uint16_t*>(c.out), c.out_nchw, c.in_scale, c.cout_real);
   return check_launch("conv_gemm16_kernel");
 }
 

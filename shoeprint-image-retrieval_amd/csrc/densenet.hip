@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <cmath>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "conv_gemm.h"
@@ -424,98 +425,29 @@ extern "C" size_t spr_densenet_workspace_bytes(const spr_densenet_plan* plan, in
   return 3 * align_up(densenet_buf_floats(plan, n, in_h, in_w) * elem, 256);
 }
 
-static int densenet_forward16(spr_densenet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
-                              int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
-                              float* out, spr_stream_t stream, unsigned char* trace);
-
-extern "C" int spr_densenet_forward(spr_densenet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
-                                    int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
-                                    void* workspace, float* out, spr_stream_t stream) {
-  if (plan && plan->compute != SPR_F32)  // the plain forward of a 16-bit plan is its trace forward with a null trace
-    return densenet_forward16(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, stream, nullptr);
-  const int ok = check_forward_args("spr_densenet_forward", plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed,
-                                    workspace, out);
-  if (ok != SPR_OK || n == 0) return ok;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const float* pk = static_cast<const float*>(packed);
-  const size_t buf_bytes = align_up(densenet_buf_floats(plan, n, in_h, in_w) * sizeof(float), 256);
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  float* cat = reinterpret_cast<float*>(ws);                 // the current block's tensor (or the stem's output)
-  float* tmp = reinterpret_cast<float*>(ws + buf_bytes);     // a dense layer's 128-channel intermediate / a transition's output
-  float* nxt = reinterpret_cast<float*>(ws + 2 * buf_bytes); // the next block's tensor
-  auto blocks_of = [](size_t total) { return dim3(static_cast<unsigned>(std::min<size_t>((total + kThreads - 1) / kThreads, 65535 * 16))); };
-  // one convolution (stride 1, no residual); pre: BatchNorm + ReLU on the operand while it is loaded
-  auto gemm = [&](int ks, const float* in, int h, int w, int cin, int cout_p, const DOp& o, int relu, float* dst, int cout_real,
-                  int lda, int ldc, int c_off, bool pre) {
-    return launch_conv_gemm(ks, 1, in, n, h, w, cin, cout_p, pk + o.w_off, pk + o.b_off, nullptr, relu, 0, dst, nullptr, cout_real,
-                            lda, ldc, c_off, pre ? pk + o.s_off : nullptr, pre ? pk + o.t_off : nullptr, s);
-  };
-  int h = (in_h + 1) / 2, w = (in_w + 1) / 2, c = 64, ld = 64;
-  int rc = SPR_OK;
-  size_t i = 0;
-  {
-    const DOp& o = plan->ops[0];
-    // the width of the first block's tensor, if there is one: the pooled stem output goes straight into its first 64 channels
-    const int next_ld = plan->ops.size() > 1 && plan->ops[1].kind == 1 ? plan->ops[1].ctot : 64;
-    float* stem_out = (o.flags & 4) ? tmp : cat;
-    rc = launch_stem(images, n, in_h, in_w, in_channels, mean3, inv_std3, pk + o.w_off, pk + o.b_off, stem_out,
-                     (o.flags & 2) ? 1 : 0, 0, s);
-    if (rc != SPR_OK) return rc;
-    if (o.flags & 4) {
-      const int hp = (h + 1) / 2, wp = (w + 1) / 2;
-      rc = launch_maxpool3(tmp, n, h, w, 64, cat, next_ld, s);
-      if (rc != SPR_OK) return rc;
-      h = hp; w = wp; ld = next_ld;
-    }
-    i = 1;
-  }
-  const float* fin_s = nullptr;
-  const float* fin_t = nullptr;
-  for (; i < plan->ops.size(); ++i) {
-    const DOp& o = plan->ops[i];
-    if (o.kind == 1) {          // BatchNorm + ReLU (operand load) -> 1x1 -> BatchNorm (folded) + ReLU
-      rc = gemm(1, cat, h, w, o.cin, 128, o, 1, tmp, 0, o.ctot, 128, 0, true);
-    } else if (o.kind == 2) {   // 3x3, its 32 channels behind the layer's input
-      rc = gemm(3, tmp, h, w, 128, 64, o, 0, cat, 32, 128, o.ctot, o.c_off, false);
-      c = o.c_off + 32; ld = o.ctot;
-    } else if (o.kind == 3) {   // BatchNorm + ReLU -> 1x1 -> 2x2 average pool into the next block's tensor
-      rc = gemm(1, cat, h, w, o.cin, o.cout, o, 0, tmp, 0, o.ctot, o.cout, 0, true);
-      if (rc != SPR_OK) return rc;
-      const int next_ld = i + 1 < plan->ops.size() && plan->ops[i + 1].kind == 1 ? plan->ops[i + 1].ctot : o.cout;
-      const size_t total = static_cast<size_t>(n) * (h / 2) * (w / 2) * o.cout;
-      hipLaunchKernelGGL(dnet_avgpool_kernel, blocks_of(total), dim3(kThreads), 0, s, tmp, h, w, o.cout, nxt, total, next_ld);
-      rc = check_launch("dnet_avgpool_kernel");
-      float* old = cat; cat = nxt; nxt = old;
-      h /= 2; w /= 2; c = o.cout; ld = next_ld;
-    } else {                    // the closing BatchNorm rides on the layout change below
-      fin_s = pk + o.s_off; fin_t = pk + o.t_off;
-    }
-    if (rc != SPR_OK) return rc;
-  }
-  const size_t total = static_cast<size_t>(n) * c * h * w;
-  hipLaunchKernelGGL(dnet_out_kernel, blocks_of(total), dim3(kThreads), 0, s, cat, h * w, c, ld, fin_s, fin_t, 0, out, total);
-  return check_launch("dnet_out_kernel");
-}
-
-// ---------------------------------------------------------------- 16-bit plans: forward and trace
 namespace {
 template <int KS, int BN>
 auto dnet_gemm16_of(int kind) {
   return kind == SPR_F16 ? dnet_gemm16_kernel<KS, SPR_F16, BN> : dnet_gemm16_kernel<KS, SPR_BF16, BN>;
 }
 
-// one convolution of a 16-bit plan: 1x1 with 64-channel tiles (cout a multiple of 64) or 3x3 -> 32 channels
-int launch_dnet_gemm16(int kind, int ks, const uint16_t* in, int64_t n, int h, int w, int cin, int lda, const float* pk,
-                       const DOp& o, bool pre, int relu, uint16_t* dst, int cout, int ldc, int c_off, hipStream_t s) {
+// one convolution of a 16-bit plan: 1x1 with 64-channel tiles (cout a multiple of 64) or 3x3 -> 32 channels; stride 1, ReLU
+// or nothing behind it, NHWC out
+int launch_dnet_gemm16(int kind, const ConvCall& c, hipStream_t s) {
+  if (c.stride != 1 || c.res || c.in_scale || c.out_nchw || c.cout_real || c.act > 1 || !c.pre_s != !c.pre_t) {
+    set_error("launch_dnet_gemm16: dnet_gemm16_kernel has no stride, residual, input factors, SiLU, NCHW result or padded cout");
+    return SPR_ERR_UNSUPPORTED;
+  }
+  const int ks = c.ks, cin = c.cin, cout = c.cout, lda = c.in_stride(), ldc = c.out_stride(), c_off = c.c_off;
   const bool ok = cin % 32 == 0 && lda % 8 == 0 && ldc % 8 == 0 && c_off % 8 == 0 && lda >= cin &&
                   ((ks == 1 && cout % 64 == 0) || (ks == 3 && cout == 32)) && c_off + cout <= ldc;
   if (!ok) { set_error("launch_dnet_gemm16: no instance for %d x %d, %d -> %d channels", ks, ks, cin, cout); return SPR_ERR_UNSUPPORTED; }
   auto kernel = ks == 1 ? dnet_gemm16_of<1, 64>(kind) : dnet_gemm16_of<3, 32>(kind);
   const int bn = ks == 1 ? 64 : 32;
-  const long long m = static_cast<long long>(n) * h * w;
+  const long long m = static_cast<long long>(c.n) * c.h * c.w;
   hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((m + kDM - 1) / kDM), static_cast<unsigned>(cout / bn)), dim3(kThreads), 0,
-                     s, in, static_cast<int>(n), h, w, cin, lda, reinterpret_cast<const uint16_t*>(pk + o.w_off), pk + o.b_off,
-                     pre ? pk + o.s_off : nullptr, pre ? pk + o.t_off : nullptr, relu, dst, ldc, c_off);
+                     s, static_cast<const uint16_t*>(c.in), static_cast<int>(c.n), c.h, c.w, cin, lda,
+                     static_cast<const uint16_t*>(c.wts), c.bias, c.pre_s, c.pre_t, c.act, static_cast<uint16_t*>(c.out), ldc, c_off);
   return check_launch("dnet_gemm16_kernel");
 }
 
@@ -552,59 +484,84 @@ TraceLayout densenet_trace_layout(const spr_densenet_plan* plan, int64_t n, int 
 }
 }  // namespace
 
-static int densenet_forward16(spr_densenet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
-                              int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
-                              float* out, spr_stream_t stream, unsigned char* trace) {
+// The forward pass of both compute types: one walk over the plan, tensors in the plan's type.  trace: null (always for an f32
+// plan), or where the records of densenet_trace_layout are copied
+static int densenet_forward(spr_densenet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                            int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
+                            float* out, spr_stream_t stream, unsigned char* trace) {
   const int ok = check_forward_args("spr_densenet_forward", plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed,
                                     workspace, out);
   if (ok != SPR_OK || n == 0) return ok;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const float* pk = static_cast<const float*>(packed);
   const int kind = plan->compute;
-  const bool f16 = kind == SPR_F16;
-  const size_t buf_bytes = align_up(densenet_buf_floats(plan, n, in_h, in_w) * sizeof(uint16_t), 256);
+  const bool f32 = kind == SPR_F32, f16 = kind == SPR_F16;
+  const size_t buf_bytes = align_up(densenet_buf_floats(plan, n, in_h, in_w) * (f32 ? sizeof(float) : sizeof(uint16_t)), 256);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
-  uint16_t* cat = reinterpret_cast<uint16_t*>(ws);                  // the current block's tensor
-  uint16_t* tmp = reinterpret_cast<uint16_t*>(ws + buf_bytes);      // the stem's output / a 128-channel intermediate / a transition's convolution
-  uint16_t* nxt = reinterpret_cast<uint16_t*>(ws + 2 * buf_bytes);  // the next block's tensor
-  auto blocks_of = [](size_t total) { return dim3(static_cast<unsigned>(std::min<size_t>((total + kThreads - 1) / kThreads, 65535 * 16))); };
+  void* cat = ws;                  // the current block's tensor (or the stem's output)
+  void* tmp = ws + buf_bytes;      // the stem's output in front of its pool / a 128-channel intermediate / a transition's convolution
+  void* nxt = ws + 2 * buf_bytes;  // the next block's tensor
+  // one convolution (stride 1, no residual) from the first cin of lda channels of `in` into channels [c_off, c_off + cout) of
+  // the ldc of `dst`; pre: BatchNorm + ReLU on the operand while it is loaded
+  auto conv = [&](const DOp& o, int ks, const void* in, int h, int w, int cin, int lda, bool pre, int act, void* dst, int cout,
+                  int ldc, int c_off) {
+    ConvCall k;
+    k.ks = ks; k.n = n; k.h = h; k.w = w; k.cin = cin; k.cout = cout; k.lda = lda; k.ldc = ldc; k.c_off = c_off;
+    k.in = in; k.wts = pk + o.w_off; k.bias = pk + o.b_off; k.act = act; k.out = dst;
+    if (pre) { k.pre_s = pk + o.s_off; k.pre_t = pk + o.t_off; }
+    if (!f32) return launch_dnet_gemm16(kind, k, s);
+    if (ks == 3) { k.cout = 64; k.cout_real = cout; }  // conv_gemm_kernel's tile: the 32 channels are packed padded to 64
+    return launch_conv_gemm(k, s);
+  };
   TraceLayout lay;
   if (trace) lay = densenet_trace_layout(plan, n, in_h, in_w);
   size_t rec = 0;
   int h = (in_h + 1) / 2, w = (in_w + 1) / 2, c = 64, ld = 64;
   int rc;
-  {  // stem (norm0 folded, ReLU) and the max pool into the first 64 channels of block 1's tensor
+  {  // stem, and its max pool into the first 64 channels of block 1's tensor (a 16-bit plan has both: block >= 5)
     const DOp& o = plan->ops[0];
-    rc = launch_stem16(kind, 7, 2, images, n, in_h, in_w, in_channels, mean3, inv_std3,
-                       reinterpret_cast<const uint16_t*>(pk + o.w_off), pk + o.b_off, 1, tmp, s);
-    if (rc == SPR_OK) rc = trace_copy(trace, &lay, rec++, tmp, s);
+    void* stem_out = (o.flags & 4) ? tmp : cat;
+    const int relu = (o.flags & 2) ? 1 : 0;
+    rc = f32 ? launch_stem(images, n, in_h, in_w, in_channels, mean3, inv_std3, pk + o.w_off, pk + o.b_off,
+                           static_cast<float*>(stem_out), relu, 0, s)
+             : launch_stem16(kind, 7, 2, images, n, in_h, in_w, in_channels, mean3, inv_std3,
+                             reinterpret_cast<const uint16_t*>(pk + o.w_off), pk + o.b_off, relu, static_cast<uint16_t*>(stem_out), s);
+    if (rc == SPR_OK) rc = trace_copy(trace, &lay, rec++, stem_out, s);
     if (rc != SPR_OK) return rc;
-    ld = next_ld(plan, 0, 64);
-    rc = launch_maxpool3_16(tmp, n, h, w, 64, cat, ld, s);
-    h = (h + 1) / 2; w = (w + 1) / 2;
-    if (rc == SPR_OK) rc = trace_copy(trace, &lay, rec++, cat, s);
-    if (rc != SPR_OK) return rc;
+    if (o.flags & 4) {
+      ld = next_ld(plan, 0, 64);
+      rc = f32 ? launch_maxpool3(static_cast<const float*>(tmp), n, h, w, 64, static_cast<float*>(cat), ld, s)
+               : launch_maxpool3_16(static_cast<const uint16_t*>(tmp), n, h, w, 64, static_cast<uint16_t*>(cat), ld, s);
+      h = (h + 1) / 2; w = (w + 1) / 2;
+      if (rc == SPR_OK) rc = trace_copy(trace, &lay, rec++, cat, s);
+      if (rc != SPR_OK) return rc;
+    }
   }
   const float* fin_s = nullptr;
   const float* fin_t = nullptr;
   for (size_t i = 1; i < plan->ops.size(); ++i) {
     const DOp& o = plan->ops[i];
-    if (o.kind == 1) {          // BatchNorm + ReLU (operand staging) -> 1x1 -> BatchNorm (folded) + ReLU
-      rc = launch_dnet_gemm16(kind, 1, cat, n, h, w, o.cin, o.ctot, pk, o, true, 1, tmp, 128, 128, 0, s);
+    if (o.kind == 1) {          // BatchNorm + ReLU (operand load) -> 1x1 -> BatchNorm (folded) + ReLU
+      rc = conv(o, 1, cat, h, w, o.cin, o.ctot, true, 1, tmp, 128, 128, 0);
       if (rc == SPR_OK) rc = trace_copy(trace, &lay, rec++, tmp, s);
     } else if (o.kind == 2) {   // 3x3, its 32 channels behind the layer's input
-      rc = launch_dnet_gemm16(kind, 3, tmp, n, h, w, 128, 128, pk, o, false, 0, cat, 32, o.ctot, o.c_off, s);
+      rc = conv(o, 3, tmp, h, w, 128, 128, false, 0, cat, 32, o.ctot, o.c_off);
       c = o.c_off + 32; ld = o.ctot;
       if (rc == SPR_OK && c == o.ctot) rc = trace_copy(trace, &lay, rec++, cat, s);
     } else if (o.kind == 3) {   // BatchNorm + ReLU -> 1x1 -> 2x2 average pool into the next block's tensor
-      rc = launch_dnet_gemm16(kind, 1, cat, n, h, w, o.cin, o.ctot, pk, o, true, 0, tmp, o.cout, o.cout, 0, s);
+      rc = conv(o, 1, cat, h, w, o.cin, o.ctot, true, 0, tmp, o.cout, o.cout, 0);
       if (rc == SPR_OK) rc = trace_copy(trace, &lay, rec++, tmp, s);
       if (rc != SPR_OK) return rc;
       ld = next_ld(plan, i, o.cout);
-      const size_t total8 = static_cast<size_t>(n) * (h / 2) * (w / 2) * o.cout / 8;
-      hipLaunchKernelGGL(f16 ? dnet_avgpool16_kernel<SPR_F16> : dnet_avgpool16_kernel<SPR_BF16>, blocks_of(total8), dim3(kThreads), 0,
-                         s, tmp, h, w, o.cout, nxt, total8, ld);
-      rc = check_launch("dnet_avgpool16_kernel");
+      const size_t total = static_cast<size_t>(n) * (h / 2) * (w / 2) * o.cout / (f32 ? 1 : 8);  // channels per work-item
+      if (f32) {
+        hipLaunchKernelGGL(dnet_avgpool_kernel, blocks_of(total), dim3(kThreads), 0, s, static_cast<const float*>(tmp), h, w, o.cout,
+                           static_cast<float*>(nxt), total, ld);
+      } else {
+        hipLaunchKernelGGL(f16 ? dnet_avgpool16_kernel<SPR_F16> : dnet_avgpool16_kernel<SPR_BF16>, blocks_of(total), dim3(kThreads), 0,
+                           s, static_cast<const uint16_t*>(tmp), h, w, o.cout, static_cast<uint16_t*>(nxt), total, ld);
+      }
+      rc = check_launch(f32 ? "dnet_avgpool_kernel" : "dnet_avgpool16_kernel");
       std::swap(cat, nxt);
       h /= 2; w /= 2; c = o.cout;
       if (rc == SPR_OK) rc = trace_copy(trace, &lay, rec++, cat, s);
@@ -614,11 +571,22 @@ static int densenet_forward16(spr_densenet_plan* plan, const uint8_t* images, in
     if (rc != SPR_OK) return rc;
   }
   const size_t total = static_cast<size_t>(n) * c * h * w;
-  hipLaunchKernelGGL(f16 ? dnet_out16_kernel<SPR_F16> : dnet_out16_kernel<SPR_BF16>, blocks_of(total), dim3(kThreads), 0, s, cat,
-                     h * w, c, ld, fin_s, fin_t, out, total);
-  rc = check_launch("dnet_out16_kernel");
+  if (f32) {
+    hipLaunchKernelGGL(dnet_out_kernel, blocks_of(total), dim3(kThreads), 0, s, static_cast<const float*>(cat), h * w, c, ld, fin_s,
+                       fin_t, 0, out, total);
+  } else {
+    hipLaunchKernelGGL(f16 ? dnet_out16_kernel<SPR_F16> : dnet_out16_kernel<SPR_BF16>, blocks_of(total), dim3(kThreads), 0, s,
+                       static_cast<const uint16_t*>(cat), h * w, c, ld, fin_s, fin_t, out, total);
+  }
+  rc = check_launch(f32 ? "dnet_out_kernel" : "dnet_out16_kernel");
   if (rc == SPR_OK) rc = trace_copy(trace, &lay, rec++, out, s);
   return rc;
+}
+
+extern "C" int spr_densenet_forward(spr_densenet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                                    int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
+                                    void* workspace, float* out, spr_stream_t stream) {
+  return densenet_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, stream, nullptr);
 }
 
 extern "C" int spr_densenet_trace_layout(const spr_densenet_plan* plan, int64_t n, int32_t in_h, int32_t in_w, int64_t* records,
@@ -633,6 +601,6 @@ extern "C" int spr_densenet_forward_trace(spr_densenet_plan* plan, const uint8_t
                                           void* workspace, float* out, void* trace, spr_stream_t stream) {
   if (!plan || !trace) { set_error("spr_densenet_forward_trace: null pointer"); return SPR_ERR_ARG; }
   if (plan->compute == SPR_F32) { set_error("spr_densenet_forward_trace: 16-bit plans only"); return SPR_ERR_UNSUPPORTED; }
-  return densenet_forward16(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, stream,
-                            static_cast<unsigned char*>(trace));
+  return densenet_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, stream,
+                          static_cast<unsigned char*>(trace));
 }

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "conv_gemm.h"
@@ -429,57 +430,71 @@ extern "C" int spr_effnet_trace_layout(const spr_effnet_plan* plan, int64_t n, i
   return trace_query(effnet_trace_layout(plan, n, in_h, in_w), records, total_bytes);
 }
 
-// The 16-bit plans' forward pass: the same walk over the flattened layers with float16 / bfloat16 activations (padded to 64
-// channels, the same four buffers: the f32 sizes are kept, half of each is used), the stem on stem16_kernel's 3x3 / stride 2
-// instance, every other convolution on conv_gemm16_kernel (SiLU in front of the residual sum, squeeze-excitation factors on
-// the operand), depthwise convolutions and the squeeze-excitation mean on their 16-bit kernels; float32 NCHW out.
-// trace: null, or where every layer's stored result is copied (effnet_trace_layout)
-static int effnet_forward16(const spr_effnet_plan* plan, const uint8_t* images, int64_t n, int in_h, int in_w, int in_channels,
-                            const float* mean3, const float* inv_std3, const float* pk, unsigned char* ws, size_t buf_bytes,
-                            float* out, hipStream_t s, unsigned char* trace) {
+// The forward pass: one walk over the flattened layers, activations in the plan's compute type (padded to 64 channels; the
+// four buffers keep their f32 sizes, a 16-bit plan uses half of each).  f32: enet_input_kernel, then every convolution (the
+// stem as an ordinary one with 16 input channels) on conv_gemm_kernel.  16-bit: the stem on stem16_kernel's 3x3 / stride 2
+// instance, every other convolution on conv_gemm16_kernel.  Both: SiLU in front of the residual sum, squeeze-excitation
+// factors on the operand, depthwise convolutions and the squeeze-excitation mean on their kernels per type; float32 NCHW out.
+// trace: null (always for an f32 plan), or where every layer's stored result is copied (effnet_trace_layout)
+static int effnet_forward(const spr_effnet_plan* plan, const uint8_t* images, int64_t n, int in_h, int in_w, int in_channels,
+                          const float* mean3, const float* inv_std3, const void* packed, void* workspace, float* out,
+                          spr_stream_t stream, unsigned char* trace) {
+  const int ok = check_forward_args(trace ? "spr_effnet_forward_trace" : "spr_effnet_forward", plan, images, n, in_h, in_w,
+                                    in_channels, mean3, inv_std3, packed, workspace, out);
+  if (ok != SPR_OK || n == 0) return ok;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const float* pk = static_cast<const float*>(packed);
   const int kind = plan->compute;
-  TraceLayout lay;
-  if (trace) lay = effnet_trace_layout(plan, n, in_h, in_w);
-  uint16_t* x = reinterpret_cast<uint16_t*>(ws);
-  uint16_t* t1 = reinterpret_cast<uint16_t*>(ws + buf_bytes);
-  uint16_t* t2 = reinterpret_cast<uint16_t*>(ws + 2 * buf_bytes);
-  uint16_t* y = reinterpret_cast<uint16_t*>(ws + 3 * buf_bytes);
+  const bool f32 = kind == SPR_F32, f16 = kind == SPR_F16;
+  const size_t buf_bytes = align_up(effnet_buf_floats(plan, n, in_h, in_w) * sizeof(float), 256);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  void* x = ws;                   // block input
+  void* y = ws + 3 * buf_bytes;   // block output
+  void* tmp[2] = {ws + buf_bytes, ws + 2 * buf_bytes};
   float* pooled = reinterpret_cast<float*>(ws + 4 * buf_bytes);
   float* factors = pooled + align_up(static_cast<size_t>(n) * plan->max_expand_p * sizeof(float), 256) / sizeof(float);
   float* hidden = factors + align_up(static_cast<size_t>(n) * plan->max_expand_p * sizeof(float), 256) / sizeof(float);
+  TraceLayout lay;
+  if (trace) lay = effnet_trace_layout(plan, n, in_h, in_w);
   int h = in_h, w = in_w;
   int rc;
-  {  // stem: 3x3 / stride 2, 3 -> 64 (padded), SiLU, pre-processing fused
+  size_t i = 0;
+  if (f32) {  // the normalised image with 16 channels: op 0 is an ordinary convolution behind it
+    const size_t pixels = static_cast<size_t>(n) * in_h * in_w;
+    hipLaunchKernelGGL(enet_input_kernel, blocks_of(pixels), dim3(kThreads), 0, s, images, pixels, in_channels, mean3[0], mean3[1],
+                       mean3[2], inv_std3[0], inv_std3[1], inv_std3[2], static_cast<float*>(x));
+    rc = check_launch("enet_input_kernel");
+    if (rc != SPR_OK) return rc;
+  } else {    // op 0 on the matrix-core stem: 3x3 / stride 2, 3 -> 64 (padded), SiLU, pre-processing fused
     const EOp& o = plan->ops[0];
     if (plan->ops.size() == 1 || o.cout_p != 64) { set_error("spr_effnet_forward: a 16-bit plan needs layers behind a 64-wide stem"); return SPR_ERR_UNSUPPORTED; }
-    const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
     rc = launch_stem16(kind, 3, 2, images, n, h, w, in_channels, mean3, inv_std3, reinterpret_cast<const uint16_t*>(pk + o.w_off),
-                       pk + o.b_off, 2, x, s);
+                       pk + o.b_off, 2, static_cast<uint16_t*>(x), s);
     if (rc == SPR_OK) rc = trace_copy(trace, &lay, 0, x, s);
     if (rc != SPR_OK) return rc;
-    h = ho; w = wo;
+    h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1;
+    i = 1;
   }
-  const uint16_t* cur = x;
-  uint16_t* tmp[2] = {t1, t2};
+  const void* cur = x;  // what the next layer reads
   int ti = 0;
   const float* scale = nullptr;
-  for (size_t i = 1; i < plan->ops.size(); ++i) {
+  for (; i < plan->ops.size(); ++i) {
     const EOp& o = plan->ops[i];
     const bool last = i + 1 == plan->ops.size();
     if (o.kind == 0) {
-      uint16_t* dst = o.block_end ? y : tmp[ti];
-      const uint16_t* res = o.res ? x : nullptr;
-      const float* sc = o.scaled ? scale : nullptr;
-      const uint16_t* w16 = reinterpret_cast<const uint16_t*>(pk + o.w_off);
-      float* o32 = last ? out : nullptr;
+      void* dst = o.block_end ? y : tmp[ti];
+      ConvCall k;
       // (cin_p, cout_p: the channel counts of the tensors = the padded widths of the layer)
-      rc = launch_conv_gemm16(kind, o.ks, o.stride, cur, n, h, w, o.cin_p, o.cout_p, w16, pk + o.b_off, res, o.act, dst, o32, sc,
-                              o.cout, false, s);
-      if (rc == SPR_OK) rc = trace_copy(trace, &lay, i, last ? static_cast<const void*>(out) : dst, s);
+      k.ks = o.ks; k.stride = o.stride; k.n = n; k.h = h; k.w = w; k.cin = o.cin_p; k.cout = o.cout_p;
+      k.cout_real = f32 && !last ? 0 : o.cout;  // (an f32 NHWC store honours it: the padded channels must be written)
+      k.in = cur; k.wts = pk + o.w_off; k.bias = pk + o.b_off; k.res = o.res ? x : nullptr; k.in_scale = o.scaled ? scale : nullptr;
+      k.act = o.act; k.out = dst; k.out_nchw = last ? out : nullptr;
+      rc = f32 ? launch_conv_gemm(k, s) : launch_conv_gemm16(kind, k, false, s);
+      if (rc == SPR_OK) rc = trace_copy(trace, &lay, i, last ? static_cast<void*>(out) : dst, s);
       if (rc != SPR_OK) return rc;
       if (o.stride == 2) { h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
-      if (o.block_end) {
-        uint16_t* old = x; x = y; y = old;
+      if (o.block_end) {  // the block's output becomes the next block's input
+        std::swap(x, y);
         cur = x;
         ti = 0;
       } else {
@@ -487,17 +502,18 @@ static int effnet_forward16(const spr_effnet_plan* plan, const uint8_t* images, 
         ti ^= 1;
       }
     } else if (o.kind == 1) {
-      uint16_t* dst = tmp[ti];
+      void* dst = tmp[ti];
       const int ho = (h - 1) / o.stride + 1, wo = (w - 1) / o.stride + 1;
-      const size_t total = static_cast<size_t>(n) * ho * wo * (o.cin_p / 8);
-      const dim3 grid(static_cast<unsigned>(std::min<size_t>((total + kThreads - 1) / kThreads, 65535 * 16)));
-      if (kind == SPR_F16)
-        hipLaunchKernelGGL(enet_dw16_kernel<SPR_F16>, grid, dim3(kThreads), 0, s, cur, static_cast<int>(n), h, w, o.cin_p, o.stride,
-                           o.ks, pk + o.w_off, pk + o.b_off, dst);
-      else
-        hipLaunchKernelGGL(enet_dw16_kernel<SPR_BF16>, grid, dim3(kThreads), 0, s, cur, static_cast<int>(n), h, w, o.cin_p, o.stride,
-                           o.ks, pk + o.w_off, pk + o.b_off, dst);
-      rc = check_launch("enet_dw16_kernel");
+      const dim3 grid = blocks_of(static_cast<size_t>(n) * ho * wo * (o.cin_p / (f32 ? 4 : 8)));  // channels per work-item
+      if (f32) {
+        hipLaunchKernelGGL(enet_dw_kernel, grid, dim3(kThreads), 0, s, static_cast<const float*>(cur), static_cast<int>(n), h, w,
+                           o.cin_p, o.stride, o.ks, pk + o.w_off, pk + o.b_off, static_cast<float*>(dst));
+      } else {
+        hipLaunchKernelGGL(f16 ? enet_dw16_kernel<SPR_F16> : enet_dw16_kernel<SPR_BF16>, grid, dim3(kThreads), 0, s,
+                           static_cast<const uint16_t*>(cur), static_cast<int>(n), h, w, o.cin_p, o.stride, o.ks, pk + o.w_off,
+                           pk + o.b_off, static_cast<uint16_t*>(dst));
+      }
+      rc = check_launch(f32 ? "enet_dw_kernel" : "enet_dw16_kernel");
       if (rc == SPR_OK) rc = trace_copy(trace, &lay, i, dst, s);
       if (rc != SPR_OK) return rc;
       h = ho; w = wo;
@@ -505,11 +521,13 @@ static int effnet_forward16(const spr_effnet_plan* plan, const uint8_t* images, 
       ti ^= 1;
     } else {
       const dim3 grid(o.cin_p / 64, static_cast<unsigned>(n));
-      if (kind == SPR_F16)
-        hipLaunchKernelGGL(enet_pool16_kernel<SPR_F16>, grid, dim3(kThreads), 0, s, cur, h * w, o.cin_p, pooled);
-      else
-        hipLaunchKernelGGL(enet_pool16_kernel<SPR_BF16>, grid, dim3(kThreads), 0, s, cur, h * w, o.cin_p, pooled);
-      rc = check_launch("enet_pool16_kernel");
+      if (f32) {
+        hipLaunchKernelGGL(enet_pool_kernel, grid, dim3(kThreads), 0, s, static_cast<const float*>(cur), h * w, o.cin_p, pooled);
+      } else {
+        hipLaunchKernelGGL(f16 ? enet_pool16_kernel<SPR_F16> : enet_pool16_kernel<SPR_BF16>, grid, dim3(kThreads), 0, s,
+                           static_cast<const uint16_t*>(cur), h * w, o.cin_p, pooled);
+      }
+      rc = check_launch(f32 ? "enet_pool_kernel" : "enet_pool16_kernel");
       if (rc != SPR_OK) return rc;
       rc = launch_enet_fc(pooled, n, o.cin_p, o.sq, pk + o.w_off, pk + o.b_off, pk + o.w2_off, pk + o.b2_off, hidden, factors, s);
       if (rc == SPR_OK) rc = trace_copy(trace, &lay, i, factors, s);
@@ -525,84 +543,12 @@ extern "C" int spr_effnet_forward_trace(spr_effnet_plan* plan, const uint8_t* im
                                         void* workspace, float* out, void* trace, spr_stream_t stream) {
   if (!plan || !trace) { set_error("spr_effnet_forward_trace: null pointer"); return SPR_ERR_ARG; }
   if (plan->compute == SPR_F32) { set_error("spr_effnet_forward_trace: 16-bit plans only"); return SPR_ERR_UNSUPPORTED; }
-  const int ok = check_forward_args("spr_effnet_forward_trace", plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed,
-                                    workspace, out);
-  if (ok != SPR_OK || n == 0) return ok;
-  const size_t buf_bytes = align_up(effnet_buf_floats(plan, n, in_h, in_w) * sizeof(float), 256);
-  return effnet_forward16(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, static_cast<const float*>(packed),
-                          static_cast<unsigned char*>(workspace), buf_bytes, out, static_cast<hipStream_t>(stream),
-                          static_cast<unsigned char*>(trace));
+  return effnet_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, stream,
+                        static_cast<unsigned char*>(trace));
 }
 
 extern "C" int spr_effnet_forward(spr_effnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
                                   int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
                                   void* workspace, float* out, spr_stream_t stream) {
-  const int ok = check_forward_args("spr_effnet_forward", plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed,
-                                    workspace, out);
-  if (ok != SPR_OK || n == 0) return ok;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const float* pk = static_cast<const float*>(packed);
-  const size_t buf_bytes = align_up(effnet_buf_floats(plan, n, in_h, in_w) * sizeof(float), 256);
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  if (plan->compute != SPR_F32)
-    return effnet_forward16(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, pk, ws, buf_bytes, out, s, nullptr);
-  float* x = reinterpret_cast<float*>(ws);                    // block input
-  float* t1 = reinterpret_cast<float*>(ws + buf_bytes);
-  float* t2 = reinterpret_cast<float*>(ws + 2 * buf_bytes);
-  float* y = reinterpret_cast<float*>(ws + 3 * buf_bytes);    // block output
-  float* pooled = reinterpret_cast<float*>(ws + 4 * buf_bytes);
-  float* factors = pooled + align_up(static_cast<size_t>(n) * plan->max_expand_p * sizeof(float), 256) / sizeof(float);
-  float* hidden = factors + align_up(static_cast<size_t>(n) * plan->max_expand_p * sizeof(float), 256) / sizeof(float);
-  const size_t pixels = static_cast<size_t>(n) * in_h * in_w;
-  hipLaunchKernelGGL(enet_input_kernel, dim3(static_cast<unsigned>(std::min<size_t>((pixels + kThreads - 1) / kThreads, 65535 * 16))),
-                     dim3(kThreads), 0, s, images, pixels, in_channels, mean3[0], mean3[1], mean3[2], inv_std3[0], inv_std3[1],
-                     inv_std3[2], x);
-  int rc = check_launch("enet_input_kernel");
-  if (rc != SPR_OK) return rc;
-  int h = in_h, w = in_w;
-  const float* cur = x;   // what the next layer reads
-  float* tmp[2] = {t1, t2};
-  int ti = 0;
-  const float* scale = nullptr;
-  for (size_t i = 0; i < plan->ops.size(); ++i) {
-    const EOp& o = plan->ops[i];
-    const bool last = i + 1 == plan->ops.size();
-    if (o.kind == 0) {
-      float* dst = last ? out : o.block_end ? y : tmp[ti];
-      const float* res = o.res ? x : nullptr;
-      const float* sc = o.scaled ? scale : nullptr;
-      rc = launch_conv_gemm(o.ks, o.stride, cur, n, h, w, o.cin_p, o.cout_p, pk + o.w_off, pk + o.b_off, res, o.act, last ? 1 : 0,
-                            dst, sc, last ? o.cout : 0, o.cin_p, o.cout_p, 0, nullptr, nullptr, s);
-      if (rc != SPR_OK) return rc;
-      if (o.stride == 2) { h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
-      if (o.block_end) {  // the block's output becomes the next block's input
-        float* old = x; x = y; y = old;
-        cur = x;
-        ti = 0;
-      } else {
-        cur = dst;
-        ti ^= 1;
-      }
-    } else if (o.kind == 1) {
-      float* dst = tmp[ti];
-      const int ho = (h - 1) / o.stride + 1, wo = (w - 1) / o.stride + 1;
-      const size_t total = static_cast<size_t>(n) * ho * wo * (o.cin_p / 4);
-      hipLaunchKernelGGL(enet_dw_kernel, dim3(static_cast<unsigned>(std::min<size_t>((total + kThreads - 1) / kThreads, 65535 * 16))),
-                         dim3(kThreads), 0, s, cur, static_cast<int>(n), h, w, o.cin_p, o.stride, o.ks, pk + o.w_off, pk + o.b_off, dst);
-      rc = check_launch("enet_dw_kernel");
-      if (rc != SPR_OK) return rc;
-      h = ho; w = wo;
-      cur = dst;
-      ti ^= 1;
-    } else {
-      hipLaunchKernelGGL(enet_pool_kernel, dim3(o.cin_p / 64, static_cast<unsigned>(n)), dim3(kThreads), 0, s, cur, h * w, o.cin_p,
-                         pooled);
-      rc = check_launch("enet_pool_kernel");
-      if (rc != SPR_OK) return rc;
-      rc = launch_enet_fc(pooled, n, o.cin_p, o.sq, pk + o.w_off, pk + o.b_off, pk + o.w2_off, pk + o.b2_off, hidden, factors, s);
-      if (rc != SPR_OK) return rc;
-      scale = factors;
-    }
-  }
-  return SPR_OK;
+  return effnet_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, stream, nullptr);
 }

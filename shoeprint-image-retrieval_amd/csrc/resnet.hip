@@ -1,5 +1,6 @@
 // ResNet50 through layer1 / layer2 / layer3 (BASELINE.json config 3: "ResNet50 layer3 summed maps") on the shared
-// convolution kernels of conv_gemm.hip: the plan, every spr_resnet_* entry point and the walks over the bottlenecks.
+// convolution kernels of conv_gemm.hip: the plan, every spr_resnet_* entry point and the walk over the bottlenecks (one for
+// both compute types).
 //
 // The reference has no ResNet (network.py:121-182 lists VGG, EfficientNet and DenseNet) and its truncation
 // `list(model.features.children())[:block]` (network.py:185) would not apply to torchvision's resnet50, which has no
@@ -13,6 +14,7 @@
 // run on vgg_conv.hip's patch kernel.  Activations NHWC between layers, NCHW float32 out of the last one.
 // Arithmetic: 17.13 GFLOP per 512x256 image through layer3; bound: fp32 MFMA 157 TFLOP/s.
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "conv_gemm.h"
@@ -165,18 +167,17 @@ extern "C" size_t spr_resnet_workspace_bytes(const spr_resnet_plan* plan, int64_
   return 4 * align_up(stem * sizeof(float), 256);
 }
 
-// one convolution of the plan on conv_gemm16_kernel (the only call sites that honour SPR_GEMM16_BN)
-static int resnet_gemm16(int kind, const RConv& c, const uint16_t* in, int64_t n, int h, int w, const float* pk,
-                         const uint16_t* res, uint16_t* out, float* out32, hipStream_t s) {
-  return launch_conv_gemm16(kind, c.ks, c.stride, in, n, h, w, c.cin, c.cout, reinterpret_cast<const uint16_t*>(pk + c.w_off),
-                            pk + c.b_off, res, c.relu, out, out32, nullptr, 0, true, s);
-}
-
-// ... and of an f32 plan on conv_gemm_kernel
-static int resnet_gemm(const RConv& c, const float* in, int64_t n, int h, int w, const float* pk, const float* res, int nchw,
-                       float* out, hipStream_t s) {
-  return launch_conv_gemm(c.ks, c.stride, in, n, h, w, c.cin, c.cout, pk + c.w_off, pk + c.b_off, res, c.relu, nchw, out,
-                          nullptr, 0, c.cin, c.cout, 0, nullptr, nullptr, s);
+// one convolution of the plan: conv_gemm_kernel for an f32 plan; in a 16-bit plan vgg_conv.hip's patch kernel for the 3x3 /
+// stride 1 layers and conv_gemm16_kernel for the others (the only call sites that honour SPR_GEMM16_BN).  out_nchw: null, or
+// where the last layer's float32 NCHW result goes
+static int resnet_conv(const spr_resnet_plan* plan, const RConv& c, const void* in, int64_t n, int h, int w, const float* pk,
+                       const void* res, void* out, float* out_nchw, hipStream_t s) {
+  ConvCall k;
+  k.ks = c.ks; k.stride = c.stride; k.n = n; k.h = h; k.w = w; k.cin = c.cin; k.cout = c.cout;
+  k.in = in; k.wts = pk + c.w_off; k.bias = pk + c.b_off; k.res = res; k.act = c.relu; k.out = out; k.out_nchw = out_nchw;
+  if (plan->compute == SPR_F32) return launch_conv_gemm(k, s);
+  if (c.ks == 3 && c.stride == 1) return launch_conv16_3x3(plan->compute, k, s);
+  return launch_conv_gemm16(plan->compute, k, true, s);
 }
 
 // stem (before pooling), max pool, then one record per convolution in conv index order (c1, c2, c3, [downsample])
@@ -210,51 +211,8 @@ extern "C" int spr_resnet_trace_layout(const spr_resnet_plan* plan, int64_t n, i
   return trace_query(resnet_trace_layout(plan, n, in_h, in_w), records, total_bytes);
 }
 
-// the bottlenecks of a 16-bit plan: x (the pooled stem output, 16-bit NHWC) lives in buf[0]; t1 / t2 / y in buf[1..3].
-// trace / lay: null, or where every convolution's stored result is copied (record 1 + conv index)
-static int resnet_blocks16(const spr_resnet_plan* plan, int64_t n, int h, int w, const float* pk, uint16_t* const buf[4],
-                           float* out, hipStream_t s, unsigned char* trace, const TraceLayout* lay) {
-  uint16_t* x = buf[0];
-  uint16_t* t1 = buf[1];
-  uint16_t* t2 = buf[2];
-  uint16_t* y = buf[3];
-  const int kind = plan->compute;
-  size_t i = 1;
-  while (i < plan->convs.size()) {
-    const RConv& c1 = plan->convs[i];
-    const RConv& c2 = plan->convs[i + 1];
-    const RConv& c3 = plan->convs[i + 2];
-    const bool down = c3.res == 2;
-    const bool last = i + (down ? 4 : 3) == plan->convs.size();
-    const int ho = c2.stride == 2 ? (h + 1) / 2 : h, wo = c2.stride == 2 ? (w + 1) / 2 : w;
-    int rc = resnet_gemm16(kind, c1, x, n, h, w, pk, nullptr, t1, nullptr, s);
-    if (rc == SPR_OK) rc = trace_copy(trace, lay, 1 + i, t1, s);
-    if (rc != SPR_OK) return rc;
-    rc = c2.stride == 2 ? resnet_gemm16(kind, c2, t1, n, h, w, pk, nullptr, t2, nullptr, s)
-                        : launch_conv16_3x3(kind, t1, n, h, w, c2.cin, c2.cout, reinterpret_cast<const uint16_t*>(pk + c2.w_off),
-                                            pk + c2.b_off, c2.relu, t2, s);
-    if (rc == SPR_OK) rc = trace_copy(trace, lay, 2 + i, t2, s);
-    if (rc != SPR_OK) return rc;
-    const uint16_t* resid = x;
-    if (down) {
-      const RConv& cd = plan->convs[i + 3];
-      rc = resnet_gemm16(kind, cd, x, n, h, w, pk, nullptr, t1, nullptr, s);
-      if (rc == SPR_OK) rc = trace_copy(trace, lay, 4 + i, t1, s);
-      if (rc != SPR_OK) return rc;
-      resid = t1;
-    }
-    rc = resnet_gemm16(kind, c3, t2, n, ho, wo, pk, resid, y, last ? out : nullptr, s);
-    if (rc == SPR_OK) rc = trace_copy(trace, lay, 3 + i, last ? static_cast<const void*>(out) : y, s);
-    if (rc != SPR_OK) return rc;
-    h = ho; w = wo;
-    uint16_t* old = x;
-    x = y;
-    y = old;
-    i += down ? 4 : 3;
-  }
-  return SPR_OK;
-}
-
+// trace: null (the plain forward; always for an f32 plan), or where the stem's, the max pool's and every convolution's stored
+// result is copied (resnet_trace_layout: record 1 + conv index)
 static int resnet_forward(spr_resnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
                           int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
                           float* out, spr_stream_t stream, unsigned char* trace) {
@@ -264,68 +222,60 @@ static int resnet_forward(spr_resnet_plan* plan, const uint8_t* images, int64_t 
   hipStream_t s = static_cast<hipStream_t>(stream);
   const float* pk = static_cast<const float*>(packed);
   const bool f32 = plan->compute == SPR_F32;
-  const size_t quarter = f32 ? spr_resnet_workspace_bytes(plan, n, in_h, in_w) / 4 : 0;
-  float* buf[4];
-  for (int i = 0; i < 4; ++i) buf[i] = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + i * quarter);
-  uint16_t* b16[4] = {nullptr, nullptr, nullptr, nullptr};
-  if (!f32) {  // [stem f32 tensor][x][t1][t2][y]
-    const size_t stem_bytes = align_up(static_cast<size_t>(n) * ((in_h + 1) / 2) * ((in_w + 1) / 2) * 64 * sizeof(float), 256);
-    buf[1] = static_cast<float*>(workspace);
-    for (int i = 0; i < 4; ++i)
-      b16[i] = reinterpret_cast<uint16_t*>(static_cast<unsigned char*>(workspace) + stem_bytes + i * resnet_big16_bytes(n, in_h, in_w));
-  }
+  // f32: four buffers, the stem's output in the second.  16-bit: [stem's tensor][x][t1][t2][y]
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  const size_t stem_bytes = align_up(static_cast<size_t>(n) * ((in_h + 1) / 2) * ((in_w + 1) / 2) * 64 * sizeof(float), 256);
+  const size_t first = f32 ? 0 : stem_bytes, step = f32 ? stem_bytes : resnet_big16_bytes(n, in_h, in_w);
+  void* x = ws + first;             // block input (first: the pooled stem output)
+  void* t1 = ws + first + step;     // conv1's output, then the downsample branch's
+  void* t2 = ws + first + 2 * step;
+  void* y = ws + first + 3 * step;  // block output
+  void* stem_out = f32 ? t1 : static_cast<void*>(ws);
   TraceLayout lay;
   if (trace) lay = resnet_trace_layout(plan, n, in_h, in_w);
-  // stem + max pool
   int h = (in_h + 1) / 2, w = (in_w + 1) / 2;
-  {
+  {  // stem + max pool
     const RConv& c = plan->convs[0];
-    int rc = f32 ? launch_stem(images, n, in_h, in_w, in_channels, mean3, inv_std3, pk + c.w_off, pk + c.b_off, buf[1], 1, 0, s)
+    int rc = f32 ? launch_stem(images, n, in_h, in_w, in_channels, mean3, inv_std3, pk + c.w_off, pk + c.b_off,
+                               static_cast<float*>(stem_out), 1, 0, s)
                  : launch_stem16(plan->compute, 7, 2, images, n, in_h, in_w, in_channels, mean3, inv_std3,
                                  reinterpret_cast<const uint16_t*>(pk + c.w_off), pk + c.b_off, 1,
-                                 reinterpret_cast<uint16_t*>(buf[1]), s);
-    if (rc == SPR_OK) rc = trace_copy(trace, &lay, 0, buf[1], s);
+                                 static_cast<uint16_t*>(stem_out), s);
+    if (rc == SPR_OK) rc = trace_copy(trace, &lay, 0, stem_out, s);
     if (rc != SPR_OK) return rc;
-    const int hp = (h + 1) / 2, wp = (w + 1) / 2;
     // (16-bit plans: the stem stored its activation rounded to the 16-bit type; the pooled tensor is layer1's operand)
-    rc = f32 ? launch_maxpool3(buf[1], n, h, w, 64, buf[0], 64, s)
-             : launch_maxpool3_16(reinterpret_cast<const uint16_t*>(buf[1]), n, h, w, 64, b16[0], 64, s);
-    if (rc == SPR_OK) rc = trace_copy(trace, &lay, 1, b16[0], s);
+    rc = f32 ? launch_maxpool3(static_cast<const float*>(stem_out), n, h, w, 64, static_cast<float*>(x), 64, s)
+             : launch_maxpool3_16(static_cast<const uint16_t*>(stem_out), n, h, w, 64, static_cast<uint16_t*>(x), 64, s);
+    if (rc == SPR_OK) rc = trace_copy(trace, &lay, 1, x, s);
     if (rc != SPR_OK) return rc;
-    h = hp; w = wp;
+    h = (h + 1) / 2; w = (w + 1) / 2;
   }
-  if (!f32) return resnet_blocks16(plan, n, h, w, pk, b16, out, s, trace, trace ? &lay : nullptr);
-  // bottlenecks: x = buf[0]
-  float* x = buf[0];
-  float* t1 = buf[1];
-  float* t2 = buf[2];
-  float* y = buf[3];
   size_t i = 1;
-  while (i < plan->convs.size()) {
+  while (i < plan->convs.size()) {  // one bottleneck
     const RConv& c1 = plan->convs[i];
     const RConv& c2 = plan->convs[i + 1];
     const RConv& c3 = plan->convs[i + 2];
     const bool down = c3.res == 2;
     const bool last = i + (down ? 4 : 3) == plan->convs.size();
     const int ho = c2.stride == 2 ? (h + 1) / 2 : h, wo = c2.stride == 2 ? (w + 1) / 2 : w;
-    int rc = resnet_gemm(c1, x, n, h, w, pk, nullptr, 0, t1, s);
+    int rc = resnet_conv(plan, c1, x, n, h, w, pk, nullptr, t1, nullptr, s);
+    if (rc == SPR_OK) rc = trace_copy(trace, &lay, 1 + i, t1, s);
     if (rc != SPR_OK) return rc;
-    rc = resnet_gemm(c2, t1, n, h, w, pk, nullptr, 0, t2, s);
+    rc = resnet_conv(plan, c2, t1, n, h, w, pk, nullptr, t2, nullptr, s);
+    if (rc == SPR_OK) rc = trace_copy(trace, &lay, 2 + i, t2, s);
     if (rc != SPR_OK) return rc;
-    const float* resid = x;
+    const void* resid = x;
     if (down) {
-      const RConv& cd = plan->convs[i + 3];
-      rc = resnet_gemm(cd, x, n, h, w, pk, nullptr, 0, t1, s);
+      rc = resnet_conv(plan, plan->convs[i + 3], x, n, h, w, pk, nullptr, t1, nullptr, s);
+      if (rc == SPR_OK) rc = trace_copy(trace, &lay, 4 + i, t1, s);
       if (rc != SPR_OK) return rc;
       resid = t1;
     }
-    float* dst = last ? out : y;
-    rc = resnet_gemm(c3, t2, n, ho, wo, pk, resid, last ? 1 : 0, dst, s);
+    rc = resnet_conv(plan, c3, t2, n, ho, wo, pk, resid, y, last ? out : nullptr, s);
+    if (rc == SPR_OK) rc = trace_copy(trace, &lay, 3 + i, last ? static_cast<void*>(out) : y, s);
     if (rc != SPR_OK) return rc;
     h = ho; w = wo;
-    float* old = x;
-    x = y;
-    y = old;
+    std::swap(x, y);
     i += down ? 4 : 3;
   }
   return SPR_OK;

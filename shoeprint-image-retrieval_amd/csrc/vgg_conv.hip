@@ -518,29 +518,32 @@ static_assert(kConvLds == kConvLdsBytes, "one LDS size");
 // in / out: NHWC 16-bit; weights as pack_conv16_3x3 writes them.
 int pack_conv16_3x3(int kind, const float* w, const float* b, float* packed, size_t w_off, size_t b_off, int cin, int cout,
                     hipStream_t s) {
-  if (kind == SPR_F16)
-    hipLaunchKernelGGL(pack_weights16_kernel<kF16>, dim3(256), dim3(kThreads), 0, s, w, b, packed, w_off, b_off, cin, cout);
-  else
-    hipLaunchKernelGGL(pack_weights16_kernel<kBF16>, dim3(256), dim3(kThreads), 0, s, w, b, packed, w_off, b_off, cin, cout);
+  auto kernel = kind == SPR_F16 ? pack_weights16_kernel<kF16> : pack_weights16_kernel<kBF16>;
+  hipLaunchKernelGGL(kernel, dim3(256), dim3(kThreads), 0, s, w, b, packed, w_off, b_off, cin, cout);
   return check_launch("pack_weights16_kernel");
 }
-int launch_conv16_3x3(int kind, const uint16_t* in, int64_t n, int h, int w, int cin, int cout, const uint16_t* w16,
-                      const float* bias, int relu, uint16_t* out, hipStream_t s) {
-  const dim3 grid(static_cast<unsigned>(ceil_div(h, kTile) * ceil_div(w, kTile)), static_cast<unsigned>(cout / kTN),
-                  static_cast<unsigned>(n));
-  if (kind == SPR_F16) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv16_kernel<kF16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(kConvLds));
-    hipLaunchKernelGGL(conv16_kernel<kF16>, grid, dim3(kThreads), kConvLds, s, in, h, w, cin, cout, w16, bias, relu, 0, 0,
-                       reinterpret_cast<float*>(out), static_cast<float*>(nullptr));
-  } else {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv16_kernel<kBF16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(kConvLds));
-    hipLaunchKernelGGL(conv16_kernel<kBF16>, grid, dim3(kThreads), kConvLds, s, in, h, w, cin, cout, w16, bias, relu, 0, 0,
-                       reinterpret_cast<float*>(out), static_cast<float*>(nullptr));
+namespace {
+// conv16_kernel for launch_conv16_3x3 and the stages of a 16-bit VGG plan: bias, ReLU, then the fused 2x2 max pool (pool) and
+// a float32 NCHW copy of the unpooled result (tap, or null); c.out_nchw: the last stage's result
+int launch_conv16(int kind, const ConvCall& c, int pool, float* tap, hipStream_t s) {
+  if (c.ks != 3 || c.stride != 1 || c.cin % kCk16 != 0 || c.cout % kTN != 0 || c.in_stride() != c.cin || c.out_stride() != c.cout ||
+      c.c_off != 0 || c.cout_real || c.res || c.in_scale || c.pre_s || c.pre_t || c.act > 1) {
+    set_error("launch_conv16_3x3: conv16_kernel is a plain 3 x 3 / stride 1 convolution with bias and ReLU (%d x %d / stride %d, "
+              "%d -> %d channels)", c.ks, c.ks, c.stride, c.cin, c.cout);
+    return SPR_ERR_UNSUPPORTED;
   }
+  auto kernel = kind == SPR_F16 ? conv16_kernel<kF16> : conv16_kernel<kBF16>;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            static_cast<int>(kConvLds));
+  const dim3 grid(static_cast<unsigned>(ceil_div(c.h, kTile) * ceil_div(c.w, kTile)), static_cast<unsigned>(c.cout / kTN),
+                  static_cast<unsigned>(c.n));
+  hipLaunchKernelGGL(kernel, grid, dim3(kThreads), kConvLds, s, static_cast<const uint16_t*>(c.in), c.h, c.w, c.cin, c.cout,
+                     static_cast<const uint16_t*>(c.wts), c.bias, c.act, pool, c.out_nchw ? 1 : 0,
+                     c.out_nchw ? c.out_nchw : static_cast<float*>(c.out), tap);
   return check_launch("conv16_kernel");
 }
+}  // namespace
+int launch_conv16_3x3(int kind, const ConvCall& c, hipStream_t s) { return launch_conv16(kind, c, 0, nullptr, s); }
 }  // namespace spr
 
 struct spr_vgg16_plan {
@@ -686,16 +689,14 @@ extern "C" int spr_vgg16_pack_weights(spr_vgg16_plan* plan, const float* const* 
       if (rc0 != SPR_OK) return rc0;
       continue;
     }
-    if (i > 0 && plan->compute == SPR_F16)
-      hipLaunchKernelGGL(pack_weights16_kernel<kF16>, dim3(256), dim3(kThreads), 0, hs, weights[i], biases[i],
-                         static_cast<float*>(packed), s.w_off, s.b_off, s.cin, s.cout);
-    else if (i > 0 && plan->compute == SPR_BF16)
-      hipLaunchKernelGGL(pack_weights16_kernel<kBF16>, dim3(256), dim3(kThreads), 0, hs, weights[i], biases[i],
-                         static_cast<float*>(packed), s.w_off, s.b_off, s.cin, s.cout);
-    else
+    int rc;
+    if (i > 0 && plan->compute != SPR_F32) {
+      rc = pack_conv16_3x3(plan->compute, weights[i], biases[i], static_cast<float*>(packed), s.w_off, s.b_off, s.cin, s.cout, hs);
+    } else {
       hipLaunchKernelGGL(pack_weights_kernel, dim3(256), dim3(kThreads), 0, hs, weights[i],
                          biases[i], static_cast<float*>(packed), s.w_off, s.b_off, s.cin, s.cout, i == 0 ? 1 : 0);
-    const int rc = check_launch("pack_weights_kernel");
+      rc = check_launch("pack_weights_kernel");
+    }
     if (rc != SPR_OK) return rc;
   }
   return SPR_OK;
@@ -775,10 +776,6 @@ static int vgg_forward(spr_vgg16_plan* plan, const uint8_t* images, int64_t n, i
                    reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + half)};
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                             static_cast<int>(kConvLds));
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv16_kernel<kF16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(kConvLds));
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv16_kernel<kBF16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(kConvLds));
   TraceLayout lay;
   if (trace) lay = vgg_trace_layout(plan, n, in_h, in_w);
   int h = in_h, w = in_w;
@@ -803,16 +800,10 @@ static int vgg_forward(spr_vgg16_plan* plan, const uint8_t* images, int64_t n, i
       const int rc = check_launch("conv_first_kernel");
       if (rc != SPR_OK) return rc;
     } else if (plan->compute != SPR_F32) {
-      const dim3 grid(tiles, static_cast<unsigned>(st.cout / kTN), static_cast<unsigned>(n));
-      const uint16_t* src16 = reinterpret_cast<const uint16_t*>(cur);
-      const uint16_t* w16 = reinterpret_cast<const uint16_t*>(pk + st.w_off);
-      if (plan->compute == SPR_F16)
-        hipLaunchKernelGGL(conv16_kernel<kF16>, grid, dim3(kThreads), kConvLds, s, src16, h, w, st.cin, st.cout, w16,
-                           pk + st.b_off, st.relu, st.pool, last ? 1 : 0, dst, tap);
-      else
-        hipLaunchKernelGGL(conv16_kernel<kBF16>, grid, dim3(kThreads), kConvLds, s, src16, h, w, st.cin, st.cout, w16,
-                           pk + st.b_off, st.relu, st.pool, last ? 1 : 0, dst, tap);
-      const int rc = check_launch("conv16_kernel");
+      ConvCall k;
+      k.ks = 3; k.n = n; k.h = h; k.w = w; k.cin = st.cin; k.cout = st.cout;
+      k.in = cur; k.wts = pk + st.w_off; k.bias = pk + st.b_off; k.act = st.relu; k.out = dst; k.out_nchw = last ? out : nullptr;
+      const int rc = launch_conv16(plan->compute, k, st.pool, tap, s);
       if (rc != SPR_OK) return rc;
     } else {
       hipLaunchKernelGGL(conv_mfma_kernel, dim3(tiles, static_cast<unsigned>(st.cout / kTN), static_cast<unsigned>(n)),

@@ -81,9 +81,10 @@ def test_emu_efficientnet_16bit(model, block, hw, compute):
     ec.check_effnet16(model, block, hw, HostDevice(), emu_library(), compute)
 
 
-@pytest.mark.parametrize("block,hw", [(1, (34, 32)), (3, (34, 32)), (5, (40, 36)), (6, (36, 40))])
+@pytest.mark.parametrize("block,hw", [(1, (34, 32)), (3, (34, 32)), (5, (40, 36)), (6, (36, 40)), (4, (34, 32))])
 def test_emu_densenet201(block, hw):
-    """DenseNet_201 truncations under emulation: the stem with and without norm0 / relu0 / pool0, the first dense block
+    """DenseNet_201 truncations under emulation: the stem with and without norm0 / relu0 / pool0 (block 4: the pooled tensor is
+    the output and keeps its own width of 64, no dense block behind it), the first dense block
     (BatchNorm + ReLU on the operand load of the 1x1 convolutions, 3x3 outputs stored into their channel range of the block
     tensor), a transition (average pool into the next block's tensor)."""
     ec.check_densenet(block, hw, HostDevice(), emu_library(), n_images=1)
