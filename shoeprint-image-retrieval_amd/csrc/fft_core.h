@@ -221,8 +221,8 @@ struct LdsTwiddles {
 struct NoSink {
   __device__ __forceinline__ void operator()(int) const {}
 };
-// `sink(pp)` is called as soon as sub-transform set pp is complete (E >= TG): a caller that stores y[pp] there does not
-// hold it in registers through the remaining phases.
+// `sink(pp)` is called as soon as sub-transform set pp is complete: a caller that stores y[pp] there does not hold it in
+// registers through the remaining phases (E >= TG; with E < TG there is one set, complete after the last phase).
 template <int E, int TG, int DIR, class Tw, int SPL, class Sink = NoSink>
 __device__ __forceinline__ void group_fft(cf (&x)[E], cf (&y)[SPL][TG], int t, const Tw& tw, cf* xbuf,
                                           const Sink& sink = Sink{}) {
@@ -270,6 +270,7 @@ __device__ __forceinline__ void group_fft(cf (&x)[E], cf (&y)[SPL][TG], int t, c
   }
   if constexpr (E < TG) {
     if (G::out_valid(t, 0)) Dft<TG, DIR>::run(y[0]);
+    sink(0);
   }
 }
 
