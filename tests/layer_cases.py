@@ -139,20 +139,21 @@ def trace_records(layout, handle, n: int, h: int, w: int):
     return [tuple(int(v) for v in rec[6 * i: 6 * i + 6]) for i in range(cnt)], total.value
 
 
-def run_guarded(dev, sizes, launch) -> list:
+def run_guarded(dev, sizes, launch, fill: int = 0xFF, seed: int = 99) -> list:
     """Buffers of `sizes` bytes inside one allocation, each 256-byte aligned between poisoned bands of GUARD bytes that must
-    stay untouched; the interiors start as all-ones bytes (NaN in every float type), so anything left unwritten shows.
-    launch(buffers) enqueues the work; returns the buffers' bytes behind it (host arrays)."""
+    stay untouched; the interiors start as `fill` bytes (all ones: NaN in every float type), so anything left unwritten shows.
+    The bands hold random bytes of `seed`.  launch(buffers) enqueues the work; returns the buffers' bytes behind it (host
+    arrays)."""
     starts, at = [], GUARD
     for sz in sizes:
         starts.append(at)
         at = (at + sz + GUARD + 255) // 256 * 256
-    host = np.random.default_rng(99).integers(0, 256, size=at + 256, dtype=np.uint8)
+    host = np.random.default_rng(seed).integers(0, 256, size=at + 256, dtype=np.uint8)
     buf = dev.to_device(host)
     shift = (-dev.ptr(buf)) % 256  # every buffer 256-byte aligned
     sl = [buf[shift + s0: shift + s0 + sz] for s0, sz in zip(starts, sizes)]
     for b in sl:
-        b[:] = 0xFF
+        b[:] = fill
     launch(sl)
     dev.synchronize()
     back = np.asarray(dev.to_host(buf))
