@@ -978,6 +978,7 @@ bool fill_geometry(NccGeom& g, const FftEntry& e, bool big) {
   if (e.six) {
     // one real-output row transform per image row on three lanes; SPR_NCC_SIX=0 keeps the four-wave kernel (A/B runs)
     if (big || env_int("SPR_NCC_SIX", 1) == 0) return false;
+    g.prep6 = env_int("SPR_PREP6", 1) != 0 ? 1 : 0;
     if (g.ih > pair6_max_rows() || g.iw > pair6_max_cols()) return false;
     g.rounds_c = 2; g.r_rows = g.ih; g.r_stride = 0; g.rounds_r = 1; g.tight = 1; g.keep_w = 0; g.nv = 24;
     g.spec_per_chan = e.spec_per_chan;
@@ -1058,6 +1059,7 @@ int launch_prep_fft(const NccGeom& g, const PlanScratch& s, const PrepCall& c) {
   if (c.n == 0) return SPR_OK;
   const FftEntry* e = find_entry(g.nh, g.nw, g.six);
   if (!e) { set_error("no FFT kernel for grid %dx%d", g.nh, g.nw); return SPR_ERR_UNSUPPORTED; }
+  if (!c.is_query && prep6_covers(g)) return launch_prep6(g, s, c);  // corner windows, channels pipelined (ncc_prep6.hip)
   return e->prep(g, s, c);
 }
 

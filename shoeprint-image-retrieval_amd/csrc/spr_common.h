@@ -42,6 +42,8 @@ struct NccGeom {
   int eh, tgh, ew, tgw;
   int big;             // 1: working set in the plan's global workspace instead of LDS (maps too large for LDS)
   int six;             // 1: prepared layouts of the six-wave pair kernel (ncc_pair6.hip)
+  int prep6;           // six-wave layout: 1 unless SPR_PREP6=0 was set when the plan was made - galleries whose windows are
+                       // corner windows are prepared by ncc_prep6.hip (0: prep_fft_kernel, for A/B runs)
   int tight;           // 1: ih <= nh/2 and iw <= nw/2 (the pruned kernel variant), 0: general variant
   int rounds_c;        // column-pass rounds of (kThreads/tgh) columns covering nw/2 columns
   int r_rows;          // rows of the intermediate LDS image kept after the column pass (ih rounded up to 8)
@@ -97,6 +99,8 @@ int launch_pair_direct(const NccGeom& g, const PlanScratch& s, const PairCall& c
 int launch_prep_fft(const NccGeom& g, const PlanScratch& s, const PrepCall& c);
 int launch_pair_fft(const NccGeom& g, const PlanScratch& s, const PairCall& c);
 int launch_pair6(const NccGeom& g, const PlanScratch& s, const PairCall& c);  // six-wave pair kernel (ncc_pair6.hip)
+bool prep6_covers(const NccGeom& g);  // gallery of a six-wave plan with corner windows (ncc_prep6.hip)
+int launch_prep6(const NccGeom& g, const PlanScratch& s, const PrepCall& c);
 int launch_prep_mfma(const NccGeom& g, const PlanScratch& s, const PrepCall& c);  // bf16 / f16 matrix cores (ncc_mfma.hip), both methods
 int launch_pair_mfma(const NccGeom& g, const PlanScratch& s, const PairCall& c);
 // Pair kernels run one workgroup per pair in tiles of `pairs_per_tile`; HIP refuses a grid of 2^32 work-items or

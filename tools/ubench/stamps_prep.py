@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Where the cycles of one gallery prep workgroup (one channel of one item, six-wave layout) go: a -DSPR_PREP_STAMPS build
-of the library (first argument) records the shader clock at its phase boundaries; also times the whole launch."""
+of the library (first argument) records the shader clock at its phase boundaries; also times the whole launch.
+tools/ubench/build_stamps_prep.sh builds libstamps_prep.so (prep_fft_kernel: run with SPR_PREP6=0) and libstamps_prep6.so
+(prep6_gallery_kernel: the second of a workgroup's eight channels; its "1/sigma" split reads row pass, column pass, slots)."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
