@@ -164,6 +164,29 @@ int spr_rank_count_greater(const float* scores, int64_t ld, int64_t n_queries, i
  * conv4_3 and conv5_3 similarities, build-defined) is fused with this on the device. */
 int spr_scores_fuse(float* dst, const float* src, int64_t n, float keep, float weight, spr_stream_t stream);
 
+/* ------------------------------------------------------------------ shortlist: top-k and peak localisation
+ * spr_topk_rows: for every query row the k best items in the ranker's order - item a before item b iff s_a > s_b, or
+ * s_a == s_b (the float ==: -0.0 and +0.0 tie) and idx_a > idx_b - so the item written at position p (1-based) is the item
+ * spr_rank_true_match ranks p.  scores: device float32 [n_queries, ld], of which columns [0, n_cols) are read.  The item
+ * index of column j is global_col0 + j when col_index is NULL (a shard of a gallery: the global index of local column 0);
+ * otherwise it is col_index[q*ld + j] (device int32 [n_queries, ld]) and columns whose entry is negative (-1) are skipped:
+ * that form merges candidate lists gathered from shards.  No index may occur twice in a row.  out_scores / out_index:
+ * device float32 / int32 [n_queries, k]; positions beyond the number of items hold score 0 and index -1 (n_cols == 0:
+ * all of them).  1 <= k <= 256 and item indices below 2^31, else SPR_ERR_ARG; scores are finite by contract
+ * (spr_ncc_score stores 0 for non-finite values).  The result does not depend on the grid: any n_queries works. */
+int spr_topk_rows(const float* scores, int64_t ld, int64_t n_queries, int64_t n_cols, const int32_t* col_index,
+                  int64_t global_col0, int32_t k, float* out_scores, int32_t* out_index, spr_stream_t stream);
+
+/* spr_maps_peak: for every pair p the peak of its channel-summed NCC maps and where it is.  maps: device float32
+ * [n_pairs, channels, h, w] (what spr_ncc_maps writes, pair after pair).  acc(y, x) = sum over c of (double)maps[p][c][y][x],
+ * added sequentially for c = 0, 1, ... starting from 0.0 (a fixed order: the result is bit-reproducible); the peak is the
+ * first maximum of acc in row-major order (numpy's argmax); out_score[p] = (float)(max / channels) - get_similarity's value,
+ * similarity.py:100-108, without the floor at 0 - and out_yx[2p], out_yx[2p + 1] = its row and column in cropped search-map
+ * coordinates: the cropped template's top-left corner lies at (y - th/2, x - tw/2).  An all-zero map gives score 0 at (0, 0).
+ * channels, h, w >= 1, else SPR_ERR_ARG; n_pairs == 0 is a no-op. */
+int spr_maps_peak(const float* maps, int64_t n_pairs, int32_t channels, int32_t h, int32_t w, float* out_score,
+                  int32_t* out_yx, spr_stream_t stream);
+
 /* ------------------------------------------------------------------ query variants (rotation / scale)
  * similarity.py:230-284 pushes every query feature map through Pillow: Image.rotate(angle) (NEAREST, no
  * expand, zero fill) or Image.resize((int(w*s), int(h*s))) (BICUBIC on mode "F").  These two entry

@@ -6,7 +6,8 @@
 Same flow: load the config, iterate the size clusters of the query set, extract features of the queries and
 of the whole gallery with the truncated network chosen for the cluster, rank every query's true match, print
 the S-scores of that cluster against the whole-data-set totals.  Additionally prints rank-1 and mAP over all
-clusters at the end.
+clusters at the end.  With ``[mi355x] shortlist = K`` it also prints, under every query's rank line, the K best gallery
+prints with score, best query variant and the offset at which the mark lies on the print.
 """
 
 import os
@@ -17,7 +18,29 @@ from shoeprint_image_retrieval_amd import feature_cache
 from shoeprint_image_retrieval_amd.dataloader import Dataloader
 from shoeprint_image_retrieval_amd.network import Model
 from shoeprint_image_retrieval_amd.parse_results import cmp_all, mean_average_precision, rank1
-from shoeprint_image_retrieval_amd.similarity import compare_maps
+from shoeprint_image_retrieval_amd.similarity import _shortlist, compare_maps, scorer_from_config
+from shoeprint_image_retrieval_amd.variants import variant_labels
+
+
+def ranks_with_shortlist(shoemark_features, shoeprint_features, matching_shoeprint_ids, config, gallery_files, k):
+    """compare_maps(..., progress=True) from ONE score matrix that also feeds the shortlist of retrieve(): the same rank line per query,
+    followed by its k best gallery prints."""
+    comp = config["comparison"]
+    scorer = scorer_from_config(config)
+    scores = scorer.score_matrix(shoemark_features, shoeprint_features, rotations=comp.get("rotations"),
+                                 scales=comp.get("scales"))
+    ranks = scorer.ranks(scores, matching_shoeprint_ids)
+    short = _shortlist(scorer, shoemark_features, shoeprint_features, scores, k, True, comp.get("rotations"), comp.get("scales"))
+    labels = variant_labels(comp.get("rotations"), comp.get("scales"))
+    for i, r in enumerate(ranks):
+        print(f"Print {i} true match ranked {r}")
+        for p, g in enumerate(short.index[i]):
+            if g < 0:
+                break
+            dy, dx = short.offset[i, p]
+            print(f"    {p + 1}. {gallery_files[g]}  score {short.score[i, p]:.4f}  {labels[short.variant[i, p]]}  "
+                  f"offset ({dy}, {dx})")
+    return ranks
 
 
 def main(config_file: str = "run.toml") -> list[int]:
@@ -45,7 +68,12 @@ def main(config_file: str = "run.toml") -> list[int]:
         else:
             print(f"Gallery features from {path}")
         print("Calculating ranks:")
-        ranks = compare_maps(shoemark_features, shoeprint_features, matching_shoeprint_ids, config, progress=True)
+        shortlist = int(config["mi355x"].get("shortlist", 0) or 0)
+        if shortlist > 0:
+            ranks = ranks_with_shortlist(shoemark_features, shoeprint_features, matching_shoeprint_ids, config,
+                                         sorted(dataloader.shoeprint_files), shortlist)
+        else:
+            ranks = compare_maps(shoemark_features, shoeprint_features, matching_shoeprint_ids, config, progress=True)
         cmp_all(list(ranks), total_shoeprints=len(dataloader.shoeprint_files),
                 total_shoemarks=len(dataloader.shoemark_files))
         all_ranks += [int(r) for r in ranks]

@@ -18,6 +18,7 @@ F32, F16, BF16 = 0, 1, 2
 NCC_AUTO, NCC_FFT, NCC_DIRECT, NCC_FFT_POW2, NCC_MFMA, NCC_MFMA_F32 = 0, 1, 2, 3, 4, 5
 METHOD_NAMES = {NCC_AUTO: "auto", NCC_FFT: "fft", NCC_DIRECT: "direct", NCC_FFT_POW2: "fft_pow2", NCC_MFMA: "mfma",
                 NCC_MFMA_F32: "mfma_f32"}
+SPR_ERR_ARG = -1
 SPR_ERR_UNSUPPORTED = -3
 
 
@@ -58,6 +59,8 @@ SIGNATURES = {
     "spr_rank_true_match": (C.c_int, [_VP, _I64, _I64, _I64, _VP, _VP, _VP]),
     "spr_rank_count_greater": (C.c_int, [_VP, _I64, _I64, _I64, _I64, _VP, _VP, _VP, _VP]),
     "spr_scores_fuse": (C.c_int, [_VP, _VP, _I64, C.c_float, C.c_float, _VP]),
+    "spr_topk_rows": (C.c_int, [_VP, _I64, _I64, _I64, _VP, _I64, _I32, _VP, _VP, _VP]),
+    "spr_maps_peak": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _VP, _VP, _VP]),
     "spr_rotate_nearest": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, C.POINTER(_I64), _VP]),
     "spr_resample_axis": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
     "spr_clahe_workspace_bytes": (_SZ, [_I64, _I32, _I32]),

@@ -3,7 +3,7 @@
 The reference reads the file with the ``toml`` package; ``tomli`` (same TOML 1.0 grammar) is what
 this image ships.  As in the reference, ``rotations = ""`` / ``scales = ""`` mean "none"
 (config.py:60-63).  Reference files stay valid: keys under ``[mi355x]`` are build-only extras
-(``dtype``, ``ncc_method``, ``max_prepared_gib``, ``weights``) and all have defaults.
+(``dtype``, ``ncc_method``, ``max_prepared_gib``, ``weights``, ``shortlist`` ...) and all have defaults.
 """
 
 from __future__ import annotations
@@ -48,6 +48,7 @@ class Mi355xConfig(TypedDict, total=False):
     weights: str
     gallery_cache: str  # directory for persisted gallery features (feature_cache.py); "" = off
     extractor_dtype: str  # "float32" (the reference's arithmetic) | "bfloat16" | "float16": compute type of the extractor
+    shortlist: int  # 1 .. 256: run_mi355x.py also prints, per query, that many best gallery prints with variant and offset
 
 
 class Config(TypedDict, total=False):
@@ -58,7 +59,8 @@ class Config(TypedDict, total=False):
 
 
 MI355X_DEFAULTS: dict[str, Any] = {"dtype": "float32", "ncc_method": "auto", "max_prepared_gib": 0.0, "weights": "",
-                                   "gallery_cache": "", "extractor_dtype": "float32", "f32_matrix_cores": False}
+                                   "gallery_cache": "", "extractor_dtype": "float32", "f32_matrix_cores": False,
+                                   "shortlist": 0}
 
 
 def normalise(raw: dict) -> Config:
@@ -68,6 +70,9 @@ def normalise(raw: dict) -> Config:
             comp[key] = None
     extra = dict(MI355X_DEFAULTS)
     extra.update(raw.get("mi355x", {}))
+    shortlist = extra["shortlist"]
+    if isinstance(shortlist, bool) or not isinstance(shortlist, int) or not 0 <= shortlist <= 256:
+        raise ValueError(f"[mi355x].shortlist = {shortlist!r}: expected an integer in [0, 256] (0 = off)")
     raw["mi355x"] = extra
     return raw  # type: ignore[return-value]
 

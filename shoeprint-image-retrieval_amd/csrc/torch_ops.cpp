@@ -4,6 +4,8 @@
 //   ncc_scores(q [Q,C,h,w], g [G,C,h',w']) -> f32 [Q,G]     compare_maps / _comparison_worker (similarity.py:129-227, :287-375)
 //   ranks(scores [Q,G], match i32 [Q])     -> i32 [Q]       _get_rank (similarity.py:378-386)
 //   extract(images u8 [N,H,W(,3)], ...)    -> f32 [N,C,h,w] Model.get_feature_maps (network.py:210-244), plain-VGG branches
+// and the shortlist behind retrieve() (build-defined: the reference returns ranks of known matches only):
+//   topk(scores [Q,G], k)                  -> (f32 [Q,k], i32 [Q,k])   the k best items of every row, in the ranker's order
 // This file is plain host C++ (no device code): every operator checks its tensors, takes PyTorch's CURRENT HIP stream and
 // calls the same extern "C" entry points the ctypes binding (_lib.py) calls, so both routes run the same kernels bit for
 // bit.  Scratch (prepared spectra, workspaces) comes from PyTorch's caching allocator on that stream; plans are cached per
@@ -151,6 +153,21 @@ at::Tensor ranks(const at::Tensor& scores, const at::Tensor& match) {
   return out;
 }
 
+// (scores [Q,k], index [Q,k]) of the k best gallery items of every row in the order of `ranks`: the item at position p
+// (1-based) is the item ranked p; slots beyond G hold score 0 and index -1.  1 <= k <= 256.
+std::tuple<at::Tensor, at::Tensor> topk(const at::Tensor& scores, int64_t k) {
+  check_device_tensor(scores, "scores");
+  TORCH_CHECK(scores.dim() == 2 && scores.scalar_type() == at::kFloat, "scores is a float32 [Q, G] matrix");
+  TORCH_CHECK(k >= 1 && k <= 256, "k = ", k, " outside [1, 256]");
+  const DeviceGuard guard(scores.device());
+  at::Tensor out_scores = at::empty({scores.size(0), k}, scores.options());
+  at::Tensor out_index = at::empty({scores.size(0), k}, scores.options().dtype(at::kInt));
+  if (scores.size(0) == 0) return {out_scores, out_index};
+  check(spr_topk_rows(scores.data_ptr<float>(), scores.size(1), scores.size(0), scores.size(1), nullptr, 0, static_cast<int32_t>(k),
+                      out_scores.data_ptr<float>(), out_index.data_ptr<int32_t>(), current_stream(scores)), "topk");
+  return {out_scores, out_index};
+}
+
 // features[:block] of a plain VGG (arch 0 VGG16, 1 VGG19, 2 VGG19_BN; network.py:121-139, :185-186) on a uint8 batch
 // [N,H,W] (grey, repeated over three planes: network.py:67) or [N,H,W,3]; `packed` = the weights as spr_vgg16_pack_weights
 // wrote them; mean / std as the reference's transforms take them (network.py:60-71); compute = spr_dtype of the plan
@@ -200,6 +217,7 @@ TORCH_LIBRARY(shoeprint_mi355x, m) {
   m.def("ncc_scores(Tensor q, Tensor g, int crop=2, str method='auto', int max_prepared_bytes=0) -> Tensor");
   m.def("ranks(Tensor scores, Tensor match) -> Tensor");
   m.def("extract(Tensor images, Tensor packed, int arch, int block, float[] mean, float[] std, int compute=0) -> Tensor");
+  m.def("topk(Tensor scores, int k) -> (Tensor, Tensor)");
 }
 
 // Backend-independent registration: the operators check for GPU tensors themselves (there is no CPU kernel to dispatch to).
@@ -207,4 +225,5 @@ TORCH_LIBRARY_IMPL(shoeprint_mi355x, CompositeExplicitAutograd, m) {
   m.impl("ncc_scores", &ncc_scores);
   m.impl("ranks", &ranks);
   m.impl("extract", &extract);
+  m.impl("topk", &topk);
 }

@@ -13,6 +13,8 @@ from __future__ import annotations
 
 import os
 
+import numpy as np
+
 
 def shard_bounds(n_items: int, world: int, rank: int) -> tuple[int, int]:
     """Contiguous slice [start, end) of rank ``rank``; the first ``n_items % world`` ranks hold one
@@ -68,6 +70,39 @@ def gather_score_blocks(local_scores, n_gallery: int, group=None):
     if all(e - s == wmax for s, e in widths):
         return recv.permute(1, 0, 2).reshape(nq, world * wmax).contiguous()
     return torch.cat([recv[r, :, : e - s] for r, (s, e) in enumerate(widths)], dim=1).contiguous()
+
+
+def gather_topk(local_scores, local_index, k: int, group=None, scorer=None):
+    """The global shortlist from per-rank shortlists, the same on every rank: (scores [Q,k] float32, index [Q,k] int32).
+
+    Every rank has called ``scorer.topk_device(block, k, global_col0=shard start)`` on its [Q, G_r] block and hands in
+    the two [Q,k] results (torch tensors; index -1 = empty slot).  ONE all_gather_into_tensor moves both (score bits and
+    indices side by side, Q*k*8 bytes per rank instead of the Q*G_r*4 of ``gather_score_blocks``), and one
+    ``topk_device(..., col_index=...)`` over the [Q, world*k] candidates merges them: the k best of the union are among
+    the k best of every shard, and the order is a total one on (score, index), so the result equals the top-k of the
+    full matrix bit for bit.  At world 1 the input is returned."""
+    import torch
+    import torch.distributed as dist
+
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return local_scores, local_index
+    if scorer is None:
+        from .similarity import default_scorer
+
+        scorer = default_scorer()
+    world = dist.get_world_size(group)
+    nq = local_scores.shape[0]
+    send = torch.cat([local_scores.contiguous().view(torch.int32), local_index.to(torch.int32)], dim=1).contiguous()
+    flat = torch.empty((world * nq, 2 * k), dtype=torch.int32, device=send.device)
+    dist.all_gather_into_tensor(flat, send, group=group)
+    recv = flat.view(world, nq, 2 * k).permute(1, 0, 2)  # [Q, world, 2k]
+    cand_s = recv[:, :, :k].reshape(nq, world * k).contiguous().view(torch.float32)
+    cand_i = recv[:, :, k:].reshape(nq, world * k).contiguous()
+    if cand_s.is_cuda:
+        return scorer.topk_device(cand_s, k, col_index=cand_i)
+    # host-memory backend (the CPU tests: gloo tensors, emulated kernels on numpy buffers)
+    top_s, top_i = scorer.topk_device(cand_s.numpy(), k, col_index=cand_i.numpy())
+    return torch.from_numpy(np.ascontiguousarray(top_s)), torch.from_numpy(np.ascontiguousarray(top_i))
 
 
 def matrix_digest(matrix) -> int:

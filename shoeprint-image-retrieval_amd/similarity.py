@@ -14,11 +14,15 @@ and ignored.  There is no CPU fallback: without the library or a GPU these funct
 
 ``NccScorer`` is the device-level interface used by ``bench.py`` and the multi-GPU driver:
 it keeps features, prepared spectra and the score matrix resident in HBM.
+
+``retrieve`` is what casework asks for and the reference cannot give (it ranks a KNOWN true match only): per query the
+k best gallery items, and for each where the mark sits on the print and under which rotation / scale variant.
 """
 
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Any, Sequence
 
 import numpy as np
@@ -230,6 +234,8 @@ class NccScorer:
         nq, ng = self.dev.shape(scores)
         if nq > 0 and self._torch_ops() is not None and scores.is_contiguous() and match_dev.is_contiguous():
             return self._torch_ops().ranks(scores, match_dev)
+        _require_contiguous(scores, "scores")
+        _require_contiguous(match_dev, "match")
         ranks = self.dev.zeros((max(nq, 1),), np.int32)
         self.lib.check(self.lib.spr_rank_true_match(self.dev.ptr(scores), ng, nq, ng, self.dev.ptr(match_dev),
                                                     self.dev.ptr(ranks), self.dev.stream()))
@@ -242,7 +248,128 @@ class NccScorer:
                                              self.dev.stream()))
         return out
 
+    def topk_device(self, scores, k: int, global_col0: int = 0, col_index=None):
+        """(scores [Q,k] float32, index [Q,k] int32), both on the device: the k best items of every row of the device
+        matrix ``scores`` [Q,G] in the ranker's order (position p holds the item ``ranks_device`` ranks p + 1; ties: the
+        larger index first).  The index of column j is ``global_col0 + j`` (a shard: the global index of its first column)
+        or, with ``col_index`` (device int32 [Q,G], -1 = empty), ``col_index[q, j]`` - the form that merges candidate
+        lists gathered from shards.  Slots beyond the number of items hold score 0 and index -1.  1 <= k <= 256."""
+        nq, ng = self.dev.shape(scores)
+        k = int(k)
+        _require_contiguous(scores, "scores")  # (the kernels take a dense [Q, G] matrix: a strided view would be misread)
+        if col_index is None and global_col0 == 0 and nq > 0 and self._torch_ops() is not None:
+            return self._torch_ops().topk(scores, k)
+        if col_index is not None:
+            _require_contiguous(col_index, "col_index")
+            if tuple(self.dev.shape(col_index)) != (nq, ng):
+                raise ValueError(f"col_index is {self.dev.shape(col_index)}, the scores are {(nq, ng)}")
+        out_s = self.dev.empty((max(nq, 1), max(k, 0)), np.float32)
+        out_i = self.dev.empty((max(nq, 1), max(k, 0)), np.int32)
+        self.lib.check(self.lib.spr_topk_rows(self.dev.ptr(scores), ng, nq, ng,
+                                              None if col_index is None else self.dev.ptr(col_index), int(global_col0), k,
+                                              self.dev.ptr(out_s), self.dev.ptr(out_i), self.dev.stream()))
+        return self.dev.narrow0(out_s, 0, nq), self.dev.narrow0(out_i, 0, nq)
+
+    def peaks_device(self, plan: _Plan, pq, pg, slots, max_bytes: int = 256 << 20):
+        """Host (score float32 [P], yx int32 [P,2]) of the pairs ``slots`` = [(query position in ``pq``, gallery position
+        in ``pg``), ...] of one plan: spr_ncc_maps of every pair into a slice of a [P_chunk, C, ih, iw] buffer (at most
+        ``max_bytes``), then ONE spr_maps_peak launch per chunk."""
+        ih, iw = plan.g_hw[0] - 2 * plan.crop, plan.g_hw[1] - 2 * plan.crop
+        per = plan.channels * ih * iw * 4
+        score = np.zeros(len(slots), np.float32)
+        yx = np.zeros((len(slots), 2), np.int32)
+        step = max(1, min(len(slots), max_bytes // per))
+        for s0 in range(0, len(slots), step):
+            part = slots[s0:s0 + step]
+            maps = self.dev.zeros((len(part), plan.channels, ih, iw), np.float32)  # (channels dead on either side stay 0)
+            for k, (qp, gp) in enumerate(part):
+                self.lib.check(self.lib.spr_ncc_maps(plan.handle, self.dev.ptr(pq) + qp * plan.query_item_bytes,
+                                                     self.dev.ptr(pg) + gp * plan.gallery_item_bytes,
+                                                     self.dev.ptr(maps) + k * per, self.dev.stream()))
+            out_s = self.dev.empty((len(part),), np.float32)
+            out_yx = self.dev.empty((len(part), 2), np.int32)
+            self.lib.check(self.lib.spr_maps_peak(self.dev.ptr(maps), len(part), plan.channels, ih, iw, self.dev.ptr(out_s),
+                                                  self.dev.ptr(out_yx), self.dev.stream()))
+            score[s0:s0 + len(part)] = self.dev.to_host(out_s)
+            yx[s0:s0 + len(part)] = self.dev.to_host(out_yx)
+        return score, yx
+
     # ------------------------------------------------------------------ list-of-arrays level
+    def locate(self, shoemark_maps, shoeprint_maps, pairs, rotations=None, scales=None):
+        """Where and under which variant every pair of ``pairs`` = [(query index, gallery index), ...] matches best:
+        host arrays (score float32 [P], variant int32 [P], yx int32 [P,2]).  Per pair and per variant list - numbered in
+        the order of ``VariantBuilder.variants``, 0 = the query as it is - the channel-summed NCC map is reduced to its
+        peak (first maximum in row-major order, cropped search-map coordinates); the variant with the largest peak wins,
+        the lowest number among equal peaks.  ``score`` is that peak over the channel count: get_similarity's value,
+        NOT floored at 0.  A second pass beside the pair kernels, which keep only the maximum: the union of the gallery
+        items the pairs name is uploaded once and prepared once per plan, ragged sets go by shape class as in
+        ``score_matrix``."""
+        return self._locate(shoemark_maps, shoeprint_maps, pairs, rotations, scales)[:3]
+
+    def _locate(self, shoemark_maps, shoeprint_maps, pairs, rotations, scales):
+        """``locate`` plus the cropped size (th, tw) int32 [P,2] of every pair's winning variant template, read off the
+        variant batches themselves."""
+        q_items, q_dev = _as_item_list(shoemark_maps)
+        g_items, g_dev = _as_item_list(shoeprint_maps)
+        if q_items is None:
+            q_items = list(self.dev.to_host(q_dev))
+        if g_items is None:
+            g_items = list(self.dev.to_host(g_dev))
+        pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        n = len(pairs)
+        best = np.full(n, -np.inf, dtype=np.float32)
+        variant = np.zeros(n, dtype=np.int32)
+        yx = np.zeros((n, 2), dtype=np.int32)
+        t_hw = np.zeros((n, 2), dtype=np.int32)
+        if n == 0:
+            return best, variant, yx, t_hw
+        if pairs.min() < 0 or pairs[:, 0].max() >= len(q_items) or pairs[:, 1].max() >= len(g_items):
+            raise IndexError("a pair names an item outside the query or gallery set")
+        q_used = sorted({int(q) for q in pairs[:, 0]})
+        g_used = sorted({int(g) for g in pairs[:, 1]})
+        q_groups = {shape: [q_used[i] for i in idx] for shape, idx in _group_by_shape([q_items[q] for q in q_used]).items()}
+        g_groups = {shape: [g_used[i] for i in idx] for shape, idx in _group_by_shape([g_items[g] for g in g_used]).items()}
+        from .variants import VariantBuilder
+
+        if self._variants is None:
+            self._variants = VariantBuilder(self.lib, self.dev)
+        q_side, q_pos = {}, {}
+        for qshape, q_idx in q_groups.items():
+            q_batch = self.dev.stack_to_device([q_items[i] for i in q_idx])
+            q_side[qshape] = [(tuple(self.dev.shape(v)[2:]), self.dev.astype_storage(v, self.storage))
+                              for v in self._variants.variants(q_batch, rotations, scales)]
+            q_pos[qshape] = {q: i for i, q in enumerate(q_idx)}
+        for gshape, g_idx in g_groups.items():
+            plans = {}
+            for qshape, vlist in q_side.items():
+                if qshape[0] != gshape[0]:
+                    raise ValueError(f"channel mismatch: query {qshape}, gallery {gshape}")
+                for vs, _ in vlist:
+                    plans[vs] = self.plan(qshape[0], vs, gshape[1:], dtype=self.storage)
+            chunk = min(self.gallery_chunk_items(p, len(g_idx), share=len(plans)) for p in plans.values())
+            for start in range(0, len(g_idx), chunk):
+                idx = g_idx[start:start + chunk]
+                g_pos = {g: i for i, g in enumerate(idx)}
+                g_batch = None
+                prepared = {}  # variant shape -> prepared gallery chunk
+                for qshape, vlist in q_side.items():
+                    sel = [i for i in range(n) if int(pairs[i, 0]) in q_pos[qshape] and int(pairs[i, 1]) in g_pos]
+                    if not sel:
+                        continue
+                    slots = [(q_pos[qshape][int(pairs[i, 0])], g_pos[int(pairs[i, 1])]) for i in sel]
+                    if g_batch is None:
+                        g_batch = self.dev.astype_storage(self.dev.stack_to_device([g_items[i] for i in idx]), self.storage)
+                    for number, (vs, v) in enumerate(vlist):
+                        plan = plans[vs]
+                        if vs not in prepared:
+                            prepared[vs] = self.prepare_gallery(plan, g_batch)
+                        score, pos = self.peaks_device(plan, self.prepare_queries(plan, v), prepared[vs], slots)
+                        better = score > best[sel]  # strictly: the lowest variant number keeps an equal peak
+                        rows = np.asarray(sel)[better]
+                        best[rows], variant[rows], yx[rows] = score[better], number, pos[better]
+                        t_hw[rows] = (vs[0] - 2 * self.crop, vs[1] - 2 * self.crop)
+        return best, variant, yx, t_hw
+
     def score_matrix(self, shoemark_maps, shoeprint_maps, accumulate_into=None, rotations=None,
                      scales=None) -> np.ndarray:
         """Host float32 [Q,G] matrix for the reference's list-of-arrays inputs, including ragged
@@ -346,6 +473,13 @@ class NccScorer:
         return ranks
 
 
+def _require_contiguous(buf, name: str) -> None:
+    """The C ABI takes dense row-major buffers: refuse a strided view instead of reading the wrong elements."""
+    check = getattr(buf, "is_contiguous", None)
+    if not (check() if check is not None else buf.flags["C_CONTIGUOUS"]):
+        raise ValueError(f"{name} must be contiguous")
+
+
 def _group_by_shape(items) -> dict[tuple, list[int]]:
     groups: dict[tuple, list[int]] = {}
     for i, a in enumerate(items):
@@ -418,6 +552,63 @@ def compare_maps(
         for i, r in enumerate(ranks):
             print(f"Print {i} true match ranked {r}")  # similarity.py:375
     return ranks
+
+
+@dataclass
+class Shortlist:
+    """What ``retrieve`` returns.  Slot [q, p] is the gallery item ranked p + 1 for query q; slots beyond the gallery size
+    hold index -1 (score 0, and with ``locate``: variant -1, peak_yx (-1, -1), offset (0, 0))."""
+
+    index: np.ndarray            # int32 [Q,k] gallery index
+    score: np.ndarray            # float32 [Q,k] its entry of the score matrix (floored at 0, maximum over variants)
+    variant: np.ndarray | None   # int32 [Q,k] number of the best query variant (variants.variant_labels names them)
+    peak_yx: np.ndarray | None   # int32 [Q,k,2] peak of that variant's channel-summed NCC map, cropped gallery-map coordinates
+    offset: np.ndarray | None    # int32 [Q,k,2] top-left corner of the cropped variant template in the cropped gallery map
+
+
+def retrieve(
+    shoemark_maps: list[np.ndarray],
+    shoeprint_maps: list[np.ndarray],
+    config: dict,
+    k: int = 10,
+    *,
+    locate: bool = True,
+    scorer: NccScorer | None = None,
+) -> Shortlist:
+    """The ``k`` best gallery items of every query (1 <= k <= 256), best first in the ranker's order, and - with
+    ``locate`` - for each of them the best query variant, the peak of its NCC map and the offset
+    ``(y - th//2, x - tw//2)`` at which the cropped ``th x tw`` variant template lies on the cropped gallery map.
+    ``config["comparison"]`` supplies rotations and scales as for ``compare_maps``."""
+    comp = config["comparison"]
+    rotations, scales = comp.get("rotations"), comp.get("scales")
+    scorer = scorer or scorer_from_config(config)
+    scores = scorer.score_matrix(shoemark_maps, shoeprint_maps, rotations=rotations, scales=scales)
+    return _shortlist(scorer, shoemark_maps, shoeprint_maps, scores, k, locate, rotations, scales)
+
+
+def _shortlist(scorer: NccScorer, shoemark_maps, shoeprint_maps, scores: np.ndarray, k: int, locate: bool, rotations,
+               scales) -> Shortlist:
+    """``retrieve`` behind its score matrix: ``scores`` is what ``scorer.score_matrix`` gave for these maps and variants
+    (run_mi355x.py ranks from the same matrix instead of scoring twice)."""
+    dev = scorer.dev
+    top_s, top_i = scorer.topk_device(dev.to_device(np.ascontiguousarray(scores, dtype=np.float32)), k)
+    out = Shortlist(dev.to_host(top_i).astype(np.int32, copy=True), dev.to_host(top_s).astype(np.float32, copy=True),
+                    None, None, None)
+    if not locate:
+        return out
+    nq, kk = out.index.shape
+    out.variant = np.full((nq, kk), -1, dtype=np.int32)
+    out.peak_yx = np.full((nq, kk, 2), -1, dtype=np.int32)
+    out.offset = np.zeros((nq, kk, 2), dtype=np.int32)
+    qs, ps = np.nonzero(out.index >= 0)
+    if len(qs) == 0:
+        return out
+    _, variant, yx, t_hw = scorer._locate(shoemark_maps, shoeprint_maps, np.stack([qs, out.index[qs, ps]], axis=1),
+                                          rotations, scales)
+    out.variant[qs, ps] = variant
+    out.peak_yx[qs, ps] = yx
+    out.offset[qs, ps] = yx - t_hw // 2
+    return out
 
 
 def get_similarity(shoemark: np.ndarray, shoeprint: np.ndarray, *, scorer: NccScorer | None = None) -> np.floating[Any]:

@@ -84,6 +84,15 @@ def resample_tables(in_size: int, out_size: int):
     return bounds, coeffs, ksize
 
 
+def variant_labels(rotations, scales) -> list[str]:
+    """A name for every variant, in the order of ``VariantBuilder.variants``: "original", "rotation 3", "scale 1.04",
+    "rotation 3, scale 1.04"."""
+    if scales is None:
+        return ["original"] + [f"rotation {r}" for r in rotations or []]
+    base = [""] + [f"rotation {r}, " for r in rotations or []]
+    return ["original"] + [f"{b}scale {s}" for b in base for s in scales]
+
+
 class VariantBuilder:
     """Applies rotations / scales to device batches [N,C,h,w] through the C ABI."""
 
