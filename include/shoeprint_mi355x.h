@@ -136,6 +136,31 @@ int spr_ncc_score(spr_ncc_plan* plan, const void* prepared_queries, int64_t n_qu
                   const void* prepared_gallery, int64_t n_gallery, float* scores, int64_t ld,
                   int64_t col0, int accumulate_max, spr_stream_t stream);
 
+/* spr_ncc_score with the position of every pair's maximum, out of the same pass (the arg-max is kept beside the max in the
+ * pair kernels' epilogue; nothing is added to their channel loop).  peak_yx / peak_tag: device int32 [n_queries, ld], indexed
+ * exactly like scores (same ld and col0); peak_tag may be NULL.
+ *  - scores receives bit for bit what spr_ncc_score writes for the same arguments.
+ *  - Let s be the pair's score (floored at 0 as ever) and p = (y << 16) | x the position of the maximum of the channel-summed
+ *    map, in cropped search-map coordinates (the convention of spr_maps_peak: the cropped template's top-left corner lies at
+ *    (y - th/2, x - tw/2)).  Among equal float32 sums the first position in row-major order wins; the reduction orders
+ *    (value, position) pairs, so the result does not depend on lane, wave or work-item order.  The sums are the kernels'
+ *    float32 channel sums, while spr_maps_peak adds the per-channel maps in float64: the two may name different pixels where
+ *    the two largest sums lie within rounding of each other.
+ *  - accumulate_max == 0: the entry becomes (s, p, tag) if s > 0, else (0, -1, -1).
+ *  - accumulate_max != 0: the entry is replaced by (s, p, tag) if s > prev, or if s == prev, s > 0 and tag < prev_tag (a
+ *    caller that walks variants in another order than their numbers still ends with the lowest number among equal scores);
+ *    otherwise it is left alone.  The caller starts the three matrices at 0 / -1 / -1.  The stored tag is read and compared
+ *    only when peak_tag is given.
+ *  - Limits and launch slicing as for spr_ncc_score.  spr_ncc_plan_has_peaks: 1 for SPR_NCC_FFT and SPR_NCC_DIRECT plans, 0
+ *    for the matrix-core methods (SPR_NCC_MFMA, SPR_NCC_MFMA_F32), whose kernels keep the maximum only: on such a plan
+ *    spr_ncc_score_peaks returns SPR_ERR_UNSUPPORTED and launches nothing (locate those pairs with spr_ncc_maps +
+ *    spr_maps_peak).  spr_ncc_score and spr_ncc_maps are unchanged. */
+int spr_ncc_plan_has_peaks(const spr_ncc_plan* plan); /* 1 / 0 */
+int spr_ncc_score_peaks(spr_ncc_plan* plan, const void* prepared_queries, int64_t n_queries,
+                        const void* prepared_gallery, int64_t n_gallery, float* scores, int32_t* peak_yx,
+                        int32_t* peak_tag, int64_t ld, int64_t col0, int accumulate_max, int32_t tag,
+                        spr_stream_t stream);
+
 /* Debug / parity entry point (scripts/summed_feature_maps.py:1-6, similarity.py:100-104):
  * per-channel NCC maps of ONE prepared query against ONE prepared gallery item, float32
  * [C, g_h-2*crop, g_w-2*crop] (device). */

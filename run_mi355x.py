@@ -18,7 +18,7 @@ from shoeprint_image_retrieval_amd import feature_cache
 from shoeprint_image_retrieval_amd.dataloader import Dataloader
 from shoeprint_image_retrieval_amd.network import Model
 from shoeprint_image_retrieval_amd.parse_results import cmp_all, mean_average_precision, rank1
-from shoeprint_image_retrieval_amd.similarity import _shortlist, compare_maps, scorer_from_config
+from shoeprint_image_retrieval_amd.similarity import compare_maps, retrieve_with_scores, scorer_from_config
 from shoeprint_image_retrieval_amd.variants import variant_labels
 
 
@@ -27,10 +27,8 @@ def ranks_with_shortlist(shoemark_features, shoeprint_features, matching_shoepri
     followed by its k best gallery prints."""
     comp = config["comparison"]
     scorer = scorer_from_config(config)
-    scores = scorer.score_matrix(shoemark_features, shoeprint_features, rotations=comp.get("rotations"),
-                                 scales=comp.get("scales"))
+    scores, short = retrieve_with_scores(shoemark_features, shoeprint_features, config, k, scorer=scorer)
     ranks = scorer.ranks(scores, matching_shoeprint_ids)
-    short = _shortlist(scorer, shoemark_features, shoeprint_features, scores, k, True, comp.get("rotations"), comp.get("scales"))
     labels = variant_labels(comp.get("rotations"), comp.get("scales"))
     for i, r in enumerate(ranks):
         print(f"Print {i} true match ranked {r}")

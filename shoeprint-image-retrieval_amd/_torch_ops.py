@@ -7,6 +7,8 @@
 * ``ranks(scores, match) -> int32 [Q]``                                                (similarity.py:378-386)
 * ``extract(images, packed, arch, block, mean, std) -> float32 [N, C, h, w]``          (network.py:210-244, plain VGG)
 * ``topk(scores, k) -> (float32 [Q, k], int32 [Q, k])``                                 (the k best items per row, ranker's order)
+* ``ncc_scores_located(q, g, crop=2, method="auto", max_prepared_bytes=0) -> (float32 [Q, G], int32 [Q, G, 2])``
+  (``ncc_scores`` and the pixel at which every pair's NCC map peaks, (-1, -1) where the score is 0; "fft" / "direct" plans)
 
 They take GPU tensors, run on PyTorch's current HIP stream and never synchronise; the ctypes route (``_lib.py``) calls the
 very same entry points.  ``SPR_TORCH_OPS=0`` keeps the host mirror on the ctypes route (A/B and parity tests).

@@ -77,7 +77,7 @@ struct spr_ncc_plan {
   hipEvent_t done = nullptr;
   hipStream_t last_stream = nullptr;
   bool used = false;
-  // (the counters are written only by the team schedule: the same test as the launcher's, pair_t in ncc_fft.hip)
+  // (the counters are written only by the team schedule: the same test as the launcher's, pair_t in ncc_fft_kernels.h)
   bool owns_scratch() const { return scratch.mfma_x || scratch.ws || (scratch.team_sync && spr::team_schedule()); }
 };
 
@@ -303,6 +303,29 @@ extern "C" int spr_ncc_score(spr_ncc_plan* plan, const void* pq, int64_t nq, con
   if (!pq || !pg || !scores) { set_error("spr_ncc_score: null pointer"); return SPR_ERR_ARG; }
   if (nq > 65535 || ng > (1 << 24)) { set_error("spr_ncc_score: too many items in one call (chunk the gallery)"); return SPR_ERR_ARG; }
   return score_pairs(plan, PairCall{pq, nq, pg, ng, scores, ld, col0, accumulate_max, nullptr, static_cast<hipStream_t>(stream)});
+}
+
+extern "C" int spr_ncc_plan_has_peaks(const spr_ncc_plan* plan) {
+  return plan && (plan->method == SPR_NCC_FFT || plan->method == SPR_NCC_DIRECT) ? 1 : 0;
+}
+
+extern "C" int spr_ncc_score_peaks(spr_ncc_plan* plan, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores,
+                                   int32_t* peak_yx, int32_t* peak_tag, int64_t ld, int64_t col0, int accumulate_max,
+                                   int32_t tag, spr_stream_t stream) {
+  if (!plan) { set_error("spr_ncc_score_peaks: null plan"); return SPR_ERR_ARG; }
+  if (!spr_ncc_plan_has_peaks(plan)) {  // before anything is launched
+    set_error("spr_ncc_score_peaks: the matrix-core methods keep the maximum only (spr_ncc_plan_has_peaks() == 0)");
+    return SPR_ERR_UNSUPPORTED;
+  }
+  if (nq < 0 || ng < 0 || col0 < 0 || ld < col0 + ng) { set_error("spr_ncc_score_peaks: bad sizes"); return SPR_ERR_ARG; }
+  if (nq == 0 || ng == 0) return SPR_OK;
+  if (!pq || !pg || !scores || !peak_yx) { set_error("spr_ncc_score_peaks: null pointer"); return SPR_ERR_ARG; }
+  if (nq > 65535 || ng > (1 << 24)) { set_error("spr_ncc_score_peaks: too many items in one call (chunk the gallery)"); return SPR_ERR_ARG; }
+  PairCall c{pq, nq, pg, ng, scores, ld, col0, accumulate_max, nullptr, static_cast<hipStream_t>(stream)};
+  c.peak_yx = peak_yx;
+  c.peak_tag = peak_tag;
+  c.tag = tag;
+  return score_pairs(plan, c);
 }
 
 extern "C" int spr_ncc_maps(spr_ncc_plan* plan, const void* pq, const void* pg, float* maps_out, spr_stream_t stream) {

@@ -59,12 +59,13 @@ prep_direct_kernel(NccGeom g, int is_query, const void* __restrict__ maps, float
   }
 }
 
-// grid = (n_gallery, n_queries)
-template <int SPT>
+// grid = (n_gallery, n_queries).  PEAKS: the form behind spr_ncc_score_peaks, an instantiation of its own
+template <int SPT, bool PEAKS>
 __global__ void __launch_bounds__(kThreads)
 pair_direct_kernel(NccGeom g, const float* __restrict__ pq, size_t q_item_floats, const float* __restrict__ pg,
                    size_t g_item_floats, float* __restrict__ scores, long long ld, long long col0, int accumulate,
-                   float* __restrict__ maps_out, int pws, int tws, unsigned t_off) {
+                   float* __restrict__ maps_out, int pws, int tws, unsigned t_off, int32_t* __restrict__ peak_yx,
+                   int32_t* __restrict__ peak_tag, int32_t tag) {
   unsigned char* lds = dyn_lds();
   float* red = reinterpret_cast<float*>(lds);
   float* P = reinterpret_cast<float*>(lds + 64);
@@ -140,6 +141,21 @@ pair_direct_kernel(NccGeom g, const float* __restrict__ pq, size_t q_item_floats
     }
   }
 
+  if constexpr (PEAKS) {  // spr_ncc_score_peaks: the same maximum with its position
+    float best = -3.0e38f;
+    int where = kNoPeak;
+#pragma unroll
+    for (int k = 0; k < SPT; ++k) {
+#pragma unroll
+      for (int j = 0; j < kStrip; ++j) {
+        if (sy[k] < g.ih && sx[k] + j < g.iw) peak_take(best, where, total[k][j], (sy[k] << 16) | (sx[k] + j));
+      }
+    }
+    block_peak(best, where, red);
+    if (tid == 0)
+      store_peak(scores, peak_yx, peak_tag, qi * ld + col0 + gi, best / static_cast<float>(g.channels), where, tag, accumulate);
+    return;
+  }
   float best = -3.0e38f;
 #pragma unroll
   for (int k = 0; k < SPT; ++k) {
@@ -201,22 +217,22 @@ int launch_prep_direct(const NccGeom& g, const PlanScratch&, const PrepCall& c) 
   return check_launch("prep_direct_kernel");
 }
 
-template <int SPT>
+template <int SPT, bool PEAKS>
 static int launch_pair_direct_t(const NccGeom& g, const PlanScratch&, const PairCall& c) {
   const DirectLds l = direct_lds(g);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pair_direct_kernel<SPT>),
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pair_direct_kernel<SPT, PEAKS>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
   // grid = (gallery, query) workgroups; HIP refuses 2^32 work-items and more along x: slices of the gallery
   const size_t g_item_floats = prepared_gallery_item_bytes(g, SPR_NCC_DIRECT) / sizeof(float);
   const int64_t max_g = pair_tiles_per_launch(1, kThreads);
   for (int64_t g0 = 0; g0 < c.ng; g0 += max_g) {
     const int64_t n = c.ng - g0 < max_g ? c.ng - g0 : max_g;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_direct_kernel<SPT>), dim3(static_cast<unsigned>(n), static_cast<unsigned>(c.nq)),
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_direct_kernel<SPT, PEAKS>), dim3(static_cast<unsigned>(n), static_cast<unsigned>(c.nq)),
                        dim3(kThreads), l.total, c.stream, g, static_cast<const float*>(c.pq),
                        prepared_query_item_bytes(g, SPR_NCC_DIRECT) / sizeof(float),
                        static_cast<const float*>(c.pg) + static_cast<size_t>(g0) * g_item_floats, g_item_floats, c.scores,
                        static_cast<long long>(c.ld), static_cast<long long>(c.col0 + g0), c.accumulate, c.maps_out, l.pws,
-                       l.tws, static_cast<unsigned>(l.t_off));
+                       l.tws, static_cast<unsigned>(l.t_off), c.peak_yx, c.peak_tag, c.tag);
     const int rc = check_launch("pair_direct_kernel");
     if (rc != SPR_OK) return rc;
   }
@@ -226,10 +242,10 @@ static int launch_pair_direct_t(const NccGeom& g, const PlanScratch&, const Pair
 int launch_pair_direct(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
   if (c.nq == 0 || c.ng == 0) return SPR_OK;
   switch (g.strips_per_thread) {
-    case 1: return launch_pair_direct_t<1>(g, s, c);
-    case 2: return launch_pair_direct_t<2>(g, s, c);
-    case 4: return launch_pair_direct_t<4>(g, s, c);
-    case 8: return launch_pair_direct_t<8>(g, s, c);
+    case 1: return c.peak_yx ? launch_pair_direct_t<1, true>(g, s, c) : launch_pair_direct_t<1, false>(g, s, c);
+    case 2: return c.peak_yx ? launch_pair_direct_t<2, true>(g, s, c) : launch_pair_direct_t<2, false>(g, s, c);
+    case 4: return c.peak_yx ? launch_pair_direct_t<4, true>(g, s, c) : launch_pair_direct_t<4, false>(g, s, c);
+    case 8: return c.peak_yx ? launch_pair_direct_t<8, true>(g, s, c) : launch_pair_direct_t<8, false>(g, s, c);
     default: set_error("direct NCC: unsupported strips per thread %d", g.strips_per_thread); return SPR_ERR_UNSUPPORTED;
   }
 }

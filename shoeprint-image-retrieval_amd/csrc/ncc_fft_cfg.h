@@ -1,5 +1,5 @@
 // Grid configurations of the FFT-method NCC kernels: which lanes hold which spectrum elements, and where a
-// prepared item keeps them (shared by the prep kernel, the 4-wave pair kernels of ncc_fft.hip and the 6-wave
+// prepared item keeps them (shared by the prep kernel, the 4-wave pair kernels of ncc_fft_kernels.h and the 6-wave
 // pair kernel of ncc_pair6.hip).
 #pragma once
 #include "fft_core.h"

@@ -1,6 +1,6 @@
 // Six-wave pair kernel of the FFT-method NCC scorer (the 192 x 96 grid: VGG16 conv3_3 maps of a 512x256 print).
 //
-// Same arithmetic as pair_fft_kernel (ncc_fft.hip): per channel, product of the two prepared half spectra ->
+// Same arithmetic as pair_fft_kernel (ncc_fft_kernels.h): per channel, product of the two prepared half spectra ->
 // inverse column transforms -> intermediate image in LDS -> inverse row transforms -> * 1/sigma -> channel sum in
 // registers -> spatial maximum (similarity.py:100-108, :355-367).  What differs is how the work lies on the CU:
 //
@@ -51,7 +51,7 @@ __device__ unsigned long long g_stamps[12 * kStampChannels * kStampPoints];
 #define SPR_STAMP(i)
 #endif
 
-constexpr int kTileQ6 = 16, kTileG6 = 16;  // pair -> workgroup tiling, as in ncc_fft.hip
+constexpr int kTileQ6 = 16, kTileG6 = 16;  // pair -> workgroup tiling, as in ncc_fft_kernels.h
 
 struct Pair6Args {
   int channels, nq, ng;
@@ -119,8 +119,9 @@ struct Six {
   static constexpr int kNyqOff = kXbOff + WAVES * kXbWave * 8;
   static constexpr int kHalfBytes = kNyqOff + 2 * 2 * C::NH * 8;  // two buffers of Nyquist columns (see the channel loop)
   // ... and shared by both
-  static constexpr int kRedOff = 2 * kHalfBytes;  // 2 x 8 floats of reduction scratch, then 2 barrier counters
-  static constexpr int kTwOff = kRedOff + 128;
+  static constexpr int kRedOff = 2 * kHalfBytes;  // 2 x 8 floats of reduction scratch, then 2 barrier counters,
+  static constexpr int kPeakOff = kRedOff + 128;  // then 2 x 8 peak positions (the peak form's second word per wave)
+  static constexpr int kTwOff = kPeakOff + 64;
   static constexpr int kCtabOff = kTwOff + C::NH * 8;
   static constexpr int kListOff = kCtabOff + 48 * 4;  // two lists of live channels (uint16), sized at launch
   static constexpr int kLdsBytes = kListOff;
@@ -128,12 +129,15 @@ struct Six {
   static_assert(kXbOff % 8 == 0 && kNyqOff % 8 == 0 && kHalfBytes % 16 == 0 && kTwOff % 8 == 0 && kCtabOff % 8 == 0, "");
 };
 
-template <class C>
+// PEAKS: the form behind spr_ncc_score_peaks is its own instantiation - the kernel is register-tight, and the plain form
+// carries nothing of it.  Only the epilogue differs.
+template <class C, bool PEAKS>
 __global__ void __launch_bounds__(2 * C::NT, 3)
 pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_bytes,
              const unsigned char* __restrict__ pg, size_t g_item_bytes, float* __restrict__ scores, long long ld,
              long long col0, float* __restrict__ maps_out, const cf* __restrict__ tw_h,
-             const float* __restrict__ ctab) {
+             const float* __restrict__ ctab, int32_t* __restrict__ peak_yx, int32_t* __restrict__ peak_tag,
+             int32_t tag) {
   using S = Six<C>;
   constexpr int NT = S::NT, RS = S::RS, XR = S::XR;
   constexpr int H2 = C::EH / 2;  // 16-byte loads per operand and column unit
@@ -471,6 +475,43 @@ pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_by
 #endif
   }
 
+  if constexpr (PEAKS) {
+    // The same maximum with its position.  Slot -> pixel as in the maps branch above: row wv * kRowGroups + grp, accumulator
+    // pp holds columns 2 ma, 2 ma + 1 (oa) and 2 mb, 2 mb + 1 (ob); a slot outside the map is not looked at.
+    const int lane = tid0 & 63;
+    const int grp = lane / 3, t3 = lane - 3 * grp;
+    const int real_row = wv * C::kRowGroups + grp;
+    const bool row_ok = grp < C::kRowGroups && real_row < g.ih;
+    float best = 0.0f;
+    int where = kNoPeak;
+#pragma unroll
+    for (int pp = 0; pp < 6; ++pp) {
+      const int n1 = t3 + 3 * pp;
+      const int ma = t3 == 2 ? n1 + 16 : n1, mb = t3 == 2 ? n1 : n1 + 16;
+      const int at = real_row << 16;
+      if (row_ok && n1 < 16) {
+        if (2 * ma < g.iw) peak_take(best, where, acc[pp][0].x, at | (2 * ma));
+        if (2 * ma + 1 < g.iw) peak_take(best, where, acc[pp][0].y, at | (2 * ma + 1));
+        if (2 * mb < g.iw) peak_take(best, where, acc[pp][1].x, at | (2 * mb));
+        if (2 * mb + 1 < g.iw) peak_take(best, where, acc[pp][1].y, at | (2 * mb + 1));
+      }
+    }
+    wave_peak(best, where);  // then over the six waves of this pair
+    int* red_pos = reinterpret_cast<int*>(lds + S::kPeakOff) + half * 8;
+    if ((tid0 & 63) == 0) {
+      red[wv] = best;
+      red_pos[wv] = where;
+    }
+    __syncthreads();
+    if (tid0 == 0 && live) {
+      float b = red[0];
+      int p = red_pos[0];
+      for (int w = 1; w < S::WAVES; ++w) peak_take(b, p, red[w], red_pos[w]);
+      store_peak(scores, peak_yx, peak_tag, static_cast<size_t>(qi) * ld + col0 + gi_item, b / static_cast<float>(g.channels), p,
+                 tag, g.accumulate);
+    }
+    return;
+  }
   // Slots outside the ih x iw map carry 1/sigma = 0 and stay 0; the score is floored at 0 anyway
   // (similarity.py:355), so they cannot change the result.
   float best = 0.0f;
@@ -506,8 +547,8 @@ size_t pair6_lds_bytes() { return Six<C6>::kLdsBytes; }
 int pair6_max_rows() { return C6::kRows6; }
 int pair6_max_cols() { return 64; }  // outputs x[2m], x[2m+1] for m < 32
 
-int launch_pair6(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
-  if (c.nq == 0 || c.ng == 0) return SPR_OK;
+template <bool PEAKS>
+static int launch_pair6_t(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
   if (!s.six_ctab) { set_error("pair6_kernel: the plan has no pre-twist table"); return SPR_ERR_ARG; }
   using S = Six<C6>;
   Pair6Args a{};
@@ -520,22 +561,27 @@ int launch_pair6(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
   const size_t lds_bytes = S::kLdsBytes + 2 * sizeof(unsigned short) * static_cast<size_t>(g.channels);
   a.prio_mode = env_int("SPR_P6_PRIO", 2);
   const int64_t tiles = static_cast<int64_t>(ceil_div(static_cast<int>(c.nq), kTileQ6)) * a.tiles_g;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pair6_kernel<C6>), hipFuncAttributeMaxDynamicSharedMemorySize,
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pair6_kernel<C6, PEAKS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             kLdsLimit);
   // HIP refuses grids of 2^32 work-items and more: launch in slices of pair tiles
   const int64_t max_tiles = pair_tiles_per_launch(kTileQ6 * kTileG6 / 2, 2 * C6::NT);
   for (int64_t t0 = 0; t0 < tiles; t0 += max_tiles) {
     const int64_t n = tiles - t0 < max_tiles ? tiles - t0 : max_tiles;
     a.tile0 = static_cast<int>(t0);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair6_kernel<C6>), dim3(static_cast<unsigned>(n * (kTileQ6 * kTileG6 / 2))), dim3(2 * C6::NT),
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair6_kernel<C6, PEAKS>), dim3(static_cast<unsigned>(n * (kTileQ6 * kTileG6 / 2))), dim3(2 * C6::NT),
                        lds_bytes, c.stream, a, static_cast<const unsigned char*>(c.pq),
                        prepared_query_item_bytes(g, SPR_NCC_FFT), static_cast<const unsigned char*>(c.pg),
                        prepared_gallery_item_bytes(g, SPR_NCC_FFT), c.scores, static_cast<long long>(c.ld),
-                       static_cast<long long>(c.col0), c.maps_out, s.tw_h, s.six_ctab);
+                       static_cast<long long>(c.col0), c.maps_out, s.tw_h, s.six_ctab, c.peak_yx, c.peak_tag, c.tag);
     const int rc = check_launch("pair6_kernel");
     if (rc != SPR_OK) return rc;
   }
   return SPR_OK;
+}
+
+int launch_pair6(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
+  if (c.nq == 0 || c.ng == 0) return SPR_OK;
+  return c.peak_yx ? launch_pair6_t<true>(g, s, c) : launch_pair6_t<false>(g, s, c);
 }
 
 }  // namespace spr

@@ -73,6 +73,11 @@ struct PairCall {
   float* scores; int64_t ld, col0; int accumulate;
   float* maps_out;  // spr_ncc_maps: the correlation map of the one pair; scores is null then
   hipStream_t stream;
+  // spr_ncc_score_peaks: where every pair's maximum lies ((y << 16) | x) and which call found it, indexed like scores;
+  // peak_yx null = plain spr_ncc_score, peak_tag may be null on its own
+  int32_t* peak_yx = nullptr;
+  int32_t* peak_tag = nullptr;
+  int32_t tag = 0;
 };
 struct PrepCall {
   bool is_query;
@@ -98,6 +103,7 @@ int launch_prep_direct(const NccGeom& g, const PlanScratch& s, const PrepCall& c
 int launch_pair_direct(const NccGeom& g, const PlanScratch& s, const PairCall& c);
 int launch_prep_fft(const NccGeom& g, const PlanScratch& s, const PrepCall& c);
 int launch_pair_fft(const NccGeom& g, const PlanScratch& s, const PairCall& c);
+int launch_pair_fft_peaks(const NccGeom& g, const PlanScratch& s, const PairCall& c);  // c.peak_yx set (ncc_fft_peaks.hip)
 int launch_pair6(const NccGeom& g, const PlanScratch& s, const PairCall& c);  // six-wave pair kernel (ncc_pair6.hip)
 bool prep6_covers(const NccGeom& g);  // gallery of a six-wave plan with corner windows (ncc_prep6.hip)
 int launch_prep6(const NccGeom& g, const PlanScratch& s, const PrepCall& c);
@@ -186,6 +192,59 @@ __device__ __forceinline__ float block_max(float v, float* scratch) {
   float s = scratch[0];
   for (int w = 1; w < NT / 64; ++w) s = fmaxf(s, scratch[w]);
   return s;
+}
+
+// Peak form of the pair kernels (spr_ncc_score_peaks): the maximum travels with its position p = (y << 16) | x, and every
+// reduction step orders (value, position) pairs - the larger value, among equal values the smaller position, i.e. the first
+// in row-major order - so the result does not depend on which slot, lane or wave is looked at first.
+constexpr int kNoPeak = 0x7fffffff;  // "no pixel yet": loses every tie against a real position
+__device__ __forceinline__ void peak_take(float& v, int& p, float ov, int op) {
+  const bool take = ov > v || (ov == v && op < p);
+  v = take ? ov : v;
+  p = take ? op : p;
+}
+__device__ __forceinline__ void wave_peak(float& v, int& p) {
+  for (int m = 32; m >= 1; m >>= 1) {
+    const float ov = shfl_xor(v, m);
+    const int op = shfl_xor(p, m);
+    peak_take(v, p, ov, op);
+  }
+}
+// `scratch` holds two words per wave: NT / 64 values, then NT / 64 positions
+template <int NT = kThreads>
+__device__ __forceinline__ void block_peak(float& v, int& p, float* scratch) {
+  wave_peak(v, p);
+  int* pos = reinterpret_cast<int*>(scratch + NT / 64);
+  const int tid = static_cast<int>(threadIdx.x);
+  __syncthreads();
+  if ((tid & 63) == 0) {
+    scratch[tid >> 6] = v;
+    pos[tid >> 6] = p;
+  }
+  __syncthreads();
+  v = scratch[0];
+  p = pos[0];
+  for (int w = 1; w < NT / 64; ++w) peak_take(v, p, scratch[w], pos[w]);
+}
+// One entry of spr_ncc_score_peaks (the contract is in the header).  s = the pair's score, p = the position of the map's
+// maximum; `scores` receives what the plain form stores.
+__device__ __forceinline__ void store_peak(float* scores, int32_t* peak_yx, int32_t* peak_tag, size_t at, float s, int p,
+                                           int32_t tag, int accumulate) {
+  const bool hit = s > 0.0f;  // (only then is p a pixel that won)
+  if (!accumulate) {
+    scores[at] = hit ? s : 0.0f;
+    peak_yx[at] = hit ? p : -1;
+    if (peak_tag) peak_tag[at] = hit ? tag : -1;
+    return;
+  }
+  const float prev = scores[at];
+  bool take = s > prev;
+  if (!take && peak_tag && hit && s == prev) take = tag < peak_tag[at];
+  if (take) {
+    scores[at] = s;
+    peak_yx[at] = hit ? p : -1;
+    if (peak_tag) peak_tag[at] = hit ? tag : -1;
+  }
 }
 
 }  // namespace spr

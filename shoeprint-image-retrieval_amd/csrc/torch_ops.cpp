@@ -6,6 +6,7 @@
 //   extract(images u8 [N,H,W(,3)], ...)    -> f32 [N,C,h,w] Model.get_feature_maps (network.py:210-244), plain-VGG branches
 // and the shortlist behind retrieve() (build-defined: the reference returns ranks of known matches only):
 //   topk(scores [Q,G], k)                  -> (f32 [Q,k], i32 [Q,k])   the k best items of every row, in the ranker's order
+//   ncc_scores_located(q, g)               -> (f32 [Q,G], i32 [Q,G,2]) ncc_scores and where every pair's NCC map peaks
 // This file is plain host C++ (no device code): every operator checks its tensors, takes PyTorch's CURRENT HIP stream and
 // calls the same extern "C" entry points the ctypes binding (_lib.py) calls, so both routes run the same kernels bit for
 // bit.  Scratch (prepared spectra, workspaces) comes from PyTorch's caching allocator on that stream; plans are cached per
@@ -95,7 +96,9 @@ spr_ncc_plan* ncc_plan(int device, int c, int qh, int qw, int gh, int gw, int cr
 
 // scores[q, g] = get_similarity(q, g) as float32, floored at 0 (similarity.py:355-367 without variants).  The prepared
 // gallery is built chunk by chunk when it would not fit `max_prepared_bytes` (0: a third of the free HBM, at most 64 GiB).
-at::Tensor ncc_scores(const at::Tensor& q, const at::Tensor& g, int64_t crop, std::string method, int64_t max_prepared_bytes) {
+// With `peaks` (int32 [Q,G], filled by spr_ncc_score_peaks with (y << 16) | x, -1 where the score is 0) the located form.
+at::Tensor ncc_scores_impl(const at::Tensor& q, const at::Tensor& g, int64_t crop, const std::string& method,
+                           int64_t max_prepared_bytes, at::Tensor* peaks) {
   check_device_tensor(q, "q");
   check_device_tensor(g, "g");
   TORCH_CHECK(q.dim() == 4 && g.dim() == 4, "q and g are [N, C, h, w] batches");
@@ -104,10 +107,13 @@ at::Tensor ncc_scores(const at::Tensor& q, const at::Tensor& g, int64_t crop, st
   const DeviceGuard guard(q.device());
   const int64_t nq = q.size(0), ng = g.size(0);
   at::Tensor scores = at::zeros({nq, ng}, q.options().dtype(at::kFloat));
+  if (peaks) *peaks = at::full({nq, ng}, -1, q.options().dtype(at::kInt));
   if (nq == 0 || ng == 0) return scores;
   spr_ncc_plan* plan = ncc_plan(q.device().index(), static_cast<int>(q.size(1)), static_cast<int>(q.size(2)), static_cast<int>(q.size(3)),
                                 static_cast<int>(g.size(2)), static_cast<int>(g.size(3)), static_cast<int>(crop), dtype_code(q, "q"),
                                 method_code(method));
+  TORCH_CHECK(!peaks || spr_ncc_plan_has_peaks(plan), "ncc_scores_located: the plan took a matrix-core method (", method,
+              "), whose kernels keep the maximum only; ask for method 'fft' or 'direct'");
   const spr_stream_t stream = current_stream(q);
   const auto bytes = q.options().dtype(at::kByte);
   const size_t q_item = spr_ncc_query_bytes(plan, 1), g_item = spr_ncc_gallery_bytes(plan, 1);
@@ -131,11 +137,32 @@ at::Tensor ncc_scores(const at::Tensor& q, const at::Tensor& g, int64_t crop, st
       if (q0 == 0 || ng > chunk)
         check(spr_ncc_prepare_gallery(plan, static_cast<const char*>(g.data_ptr()) + static_cast<size_t>(start) * g_stride, n,
                                       pg.data_ptr(), stream), "ncc_scores (prepare gallery)");
-      check(spr_ncc_score(plan, pq.data_ptr(), qn, pg.data_ptr(), n, scores.data_ptr<float>() + q0 * ng, ng, start, 0, stream),
-            "ncc_scores (score)");
+      if (peaks)
+        check(spr_ncc_score_peaks(plan, pq.data_ptr(), qn, pg.data_ptr(), n, scores.data_ptr<float>() + q0 * ng,
+                                  peaks->data_ptr<int32_t>() + q0 * ng, nullptr, ng, start, 0, 0, stream),
+              "ncc_scores_located (score)");
+      else
+        check(spr_ncc_score(plan, pq.data_ptr(), qn, pg.data_ptr(), n, scores.data_ptr<float>() + q0 * ng, ng, start, 0, stream),
+              "ncc_scores (score)");
     }
   }
   return scores;
+}
+
+at::Tensor ncc_scores(const at::Tensor& q, const at::Tensor& g, int64_t crop, std::string method, int64_t max_prepared_bytes) {
+  return ncc_scores_impl(q, g, crop, method, max_prepared_bytes, nullptr);
+}
+
+// ncc_scores and, out of the same pass (spr_ncc_score_peaks), the pixel (y, x) of the cropped gallery map at which every
+// pair's channel-summed NCC map peaks: int32 [Q,G,2], (-1, -1) where the score is 0.  Methods without a peak form (the
+// matrix cores) are refused.
+std::tuple<at::Tensor, at::Tensor> ncc_scores_located(const at::Tensor& q, const at::Tensor& g, int64_t crop, std::string method,
+                                                      int64_t max_prepared_bytes) {
+  at::Tensor packed;
+  at::Tensor scores = ncc_scores_impl(q, g, crop, method, max_prepared_bytes, &packed);
+  at::Tensor yx = at::stack({at::bitwise_right_shift(packed, 16), at::bitwise_and(packed, 0xFFFF)}, -1);
+  yx = at::where(packed.unsqueeze(-1) < 0, at::full({}, -1, yx.options()), yx);
+  return {scores, yx.contiguous()};
 }
 
 // ranks[q] = 1-based place of gallery item match[q] in the descending order of row q (similarity.py:378-386; ties as a
@@ -218,6 +245,7 @@ TORCH_LIBRARY(shoeprint_mi355x, m) {
   m.def("ranks(Tensor scores, Tensor match) -> Tensor");
   m.def("extract(Tensor images, Tensor packed, int arch, int block, float[] mean, float[] std, int compute=0) -> Tensor");
   m.def("topk(Tensor scores, int k) -> (Tensor, Tensor)");
+  m.def("ncc_scores_located(Tensor q, Tensor g, int crop=2, str method='auto', int max_prepared_bytes=0) -> (Tensor, Tensor)");
 }
 
 // Backend-independent registration: the operators check for GPU tensors themselves (there is no CPU kernel to dispatch to).
@@ -226,4 +254,5 @@ TORCH_LIBRARY_IMPL(shoeprint_mi355x, CompositeExplicitAutograd, m) {
   m.impl("ranks", &ranks);
   m.impl("extract", &extract);
   m.impl("topk", &topk);
+  m.impl("ncc_scores_located", &ncc_scores_located);
 }

@@ -62,6 +62,7 @@ class _Plan:
         self.fft_size = (rows.value, cols.value)
         self.query_item_bytes = lib.spr_ncc_query_bytes(handle, 1)
         self.gallery_item_bytes = lib.spr_ncc_gallery_bytes(handle, 1)
+        self.has_peaks = bool(lib.spr_ncc_plan_has_peaks(handle))  # spr_ncc_score_peaks: FFT and direct plans
 
     def close(self):
         if self.handle:
@@ -168,10 +169,19 @@ class NccScorer:
         return out
 
     def score_prepared(self, plan: _Plan, pq, nq: int, pg, ng: int, scores, ld: int, col0: int,
-                       accumulate_max: bool = False):
-        self.lib.check(self.lib.spr_ncc_score(plan.handle, self.dev.ptr(pq), nq, self.dev.ptr(pg), ng,
-                                              self.dev.ptr(scores), ld, col0, 1 if accumulate_max else 0,
-                                              self.dev.stream()))
+                       accumulate_max: bool = False, peaks=None, tags=None, tag: int = 0):
+        """spr_ncc_score; with ``peaks`` (device int32, laid out like ``scores``) spr_ncc_score_peaks: the same scores and
+        beside each the position ``(y << 16) | x`` of its maximum, in ``tags`` (optional, same layout) the ``tag`` of the
+        call that stored it.  Plans of the matrix-core methods have no peak form (``plan.has_peaks``): SprError."""
+        if peaks is None:
+            self.lib.check(self.lib.spr_ncc_score(plan.handle, self.dev.ptr(pq), nq, self.dev.ptr(pg), ng,
+                                                  self.dev.ptr(scores), ld, col0, 1 if accumulate_max else 0,
+                                                  self.dev.stream()))
+            return
+        self.lib.check(self.lib.spr_ncc_score_peaks(plan.handle, self.dev.ptr(pq), nq, self.dev.ptr(pg), ng,
+                                                    self.dev.ptr(scores), self.dev.ptr(peaks),
+                                                    None if tags is None else self.dev.ptr(tags), ld, col0,
+                                                    1 if accumulate_max else 0, int(tag), self.dev.stream()))
 
     def gallery_chunk_items(self, plan: _Plan, n_gallery: int, share: int = 1) -> int:
         """Gallery items per prepared chunk; ``share`` = how many prepared forms of the chunk are alive at once (one per
@@ -382,14 +392,48 @@ class NccScorer:
         if q_items is None and g_items is None and rotations is None and scales is None:
             scores = self.scores_device(q_dev, g_dev)
             return self.dev.to_host(scores)
+        return self._walk(q_items, q_dev, g_items, g_dev, accumulate_into, rotations, scales, False)[0]
+
+    def score_matrix_located(self, shoemark_maps, shoeprint_maps, rotations=None, scales=None):
+        """``score_matrix`` with, for every pair, the variant that gave its score and where that variant's NCC map peaks:
+        host ``(scores float32 [Q,G], variant int32 [Q,G], yx int32 [Q,G,2])``, out of the scoring pass itself
+        (spr_ncc_score_peaks) - same grouping by shape, variant lists (numbered as ``VariantBuilder.variants`` /
+        ``variant_labels``), gallery chunks and budget sharing, and bit for bit the same ``scores``.  ``yx`` is in cropped
+        search-map coordinates; the lowest variant number wins among equal scores.  A pair whose score is 0 (no variant's
+        map rises above 0) has variant -1 and yx (-1, -1).  The arg-max is taken on the kernels' float32 channel sums,
+        ``locate`` sums the per-channel maps in float64: the two may name different pixels where the two largest sums lie
+        within rounding of each other.  Plans without a peak form (the matrix-core methods) are scored as ever and their
+        blocks located by the second pass of ``locate``."""
+        return self._score_matrix_located(shoemark_maps, shoeprint_maps, rotations, scales)[:3]
+
+    def _score_matrix_located(self, shoemark_maps, shoeprint_maps, rotations, scales, fill_unfused: bool = True):
+        """``score_matrix_located`` plus the cropped template size (th, tw) int32 [Q,V,2] of every query's variants.
+        ``fill_unfused`` False leaves the blocks of plans without a peak form at variant -1 / yx (-1, -1) instead of
+        running the second pass over ALL their pairs: ``retrieve`` locates only the pairs it shortlists."""
+        q_items, q_dev = _as_item_list(shoemark_maps)
+        g_items, g_dev = _as_item_list(shoeprint_maps)
+        return self._walk(q_items, q_dev, g_items, g_dev, None, rotations, scales, True, fill_unfused)
+
+    def _walk(self, q_items, q_dev, g_items, g_dev, accumulate_into, rotations, scales, located: bool,
+              fill_unfused: bool = True):
+        """The list-of-arrays scoring walk behind ``score_matrix`` (``located`` False: plain spr_ncc_score launches, the
+        last three results are None) and ``score_matrix_located``: (scores, variant, yx, t_hw)."""
         if q_items is None:
             q_items = list(self.dev.to_host(q_dev))
         if g_items is None:
             g_items = list(self.dev.to_host(g_dev))
         nq, ng = len(q_items), len(g_items)
         out = np.zeros((nq, ng), dtype=np.float32) if accumulate_into is None else accumulate_into
+        variant = yx = t_hw = None
+        if located:
+            from .variants import variant_labels
+
+            variant = np.full((nq, ng), -1, dtype=np.int32)
+            yx = np.full((nq, ng, 2), -1, dtype=np.int32)
+            t_hw = np.zeros((nq, len(variant_labels(rotations, scales)), 2), dtype=np.int32)
+            second_pass = []  # blocks (query indices, gallery indices) one of whose plans has no peak form
         if nq == 0 or ng == 0:
-            return out
+            return out, variant, yx, t_hw
         q_groups = _group_by_shape(q_items)
         g_groups = _group_by_shape(g_items)
         from .variants import VariantBuilder
@@ -403,8 +447,11 @@ class NccScorer:
         for qshape, q_idx in q_groups.items():
             q_batch = self.dev.stack_to_device([q_items[i] for i in q_idx])
             by_shape: dict[tuple, list] = {}  # variants of one shape share a plan and the prepared gallery
-            for v in builder.variants(q_batch, rotations, scales):
-                by_shape.setdefault(tuple(self.dev.shape(v)[2:]), []).append(self.dev.astype_storage(v, self.storage))
+            for number, v in enumerate(builder.variants(q_batch, rotations, scales)):
+                vs = tuple(self.dev.shape(v)[2:])
+                by_shape.setdefault(vs, []).append((number, self.dev.astype_storage(v, self.storage)))
+                if located:
+                    t_hw[q_idx, number] = (vs[0] - 2 * self.crop, vs[1] - 2 * self.crop)
             q_side[qshape] = by_shape
         for gshape, g_idx in g_groups.items():
             plans = {}
@@ -422,18 +469,36 @@ class NccScorer:
                 prepared = {}  # plan -> prepared gallery chunk
                 for qshape, q_idx in q_groups.items():
                     sub = self.dev.zeros((len(q_idx), len(idx)), np.float32)
+                    fused = located and all(plans[vs].has_peaks for vs in q_side[qshape])
+                    sub_yx = sub_tag = None
+                    if fused:
+                        sub_yx = self.dev.to_device(np.full((len(q_idx), len(idx)), -1, dtype=np.int32))
+                        sub_tag = self.dev.to_device(np.full((len(q_idx), len(idx)), -1, dtype=np.int32))
+                    elif located:
+                        second_pass.append((q_idx, idx))
                     for vs, vlist in q_side[qshape].items():
                         plan = plans[vs]
                         if vs not in prepared:
                             prepared[vs] = self.prepare_gallery(plan, g_batch)
-                        for v in vlist:
+                        for number, v in vlist:
                             pq = self.prepare_queries(plan, v)
                             self.score_prepared(plan, pq, len(q_idx), prepared[vs], len(idx), sub, len(idx), 0,
-                                                accumulate_max=True)
+                                                accumulate_max=True, peaks=sub_yx, tags=sub_tag, tag=number)
                     sub_h = self.dev.to_host(sub)
                     block = out[np.ix_(q_idx, idx)]
                     out[np.ix_(q_idx, idx)] = np.maximum(block, sub_h)
-        return out
+                    if fused:
+                        packed = self.dev.to_host(sub_yx).astype(np.int32, copy=False)
+                        variant[np.ix_(q_idx, idx)] = self.dev.to_host(sub_tag)
+                        yx[np.ix_(q_idx, idx)] = np.where((packed < 0)[..., None], -1,
+                                                         np.stack([packed >> 16, packed & 0xFFFF], axis=-1))
+        if located and second_pass and fill_unfused:
+            pairs = np.array([(q, g) for q_idx, idx in second_pass for q in q_idx for g in idx], dtype=np.int64)
+            _, p_variant, p_yx, _ = self._locate(q_items, g_items, pairs, rotations, scales)
+            hit = out[pairs[:, 0], pairs[:, 1]] > 0  # (as the fused form: no position where the floored score is 0)
+            variant[pairs[hit, 0], pairs[hit, 1]] = p_variant[hit]
+            yx[pairs[hit, 0], pairs[hit, 1]] = p_yx[hit]
+        return out, variant, yx, t_hw
 
     def multi_layer_scores_device(self, layers, out=None):
         """Device [Q,G] float32 mean over feature layers of the per-layer score matrices (e.g.
@@ -581,15 +646,34 @@ def retrieve(
     ``config["comparison"]`` supplies rotations and scales as for ``compare_maps``."""
     comp = config["comparison"]
     rotations, scales = comp.get("rotations"), comp.get("scales")
+    return retrieve_with_scores(shoemark_maps, shoeprint_maps, config, k, locate=locate, scorer=scorer)[1]
+
+
+def retrieve_with_scores(shoemark_maps, shoeprint_maps, config: dict, k: int = 10, *, locate: bool = True,
+                         scorer: NccScorer | None = None) -> tuple[np.ndarray, Shortlist]:
+    """``retrieve`` together with the host float32 [Q,G] score matrix it was taken from (what ``score_matrix`` gives for
+    these maps and variants, bit for bit): one scoring pass serves ranks of known matches and the shortlist
+    (run_mi355x.py).  With ``locate`` the pass is ``score_matrix_located``'s list-of-arrays walk - device-resident
+    batches are copied to the host and uploaded again by shape group, where ``locate=False`` keeps ``score_matrix``'s
+    device route - and blocks of plans without a peak form are not filled: their shortlisted pairs, Q*k of them, go
+    through the second pass as entries with score 0 do."""
+    comp = config["comparison"]
+    rotations, scales = comp.get("rotations"), comp.get("scales")
     scorer = scorer or scorer_from_config(config)
-    scores = scorer.score_matrix(shoemark_maps, shoeprint_maps, rotations=rotations, scales=scales)
-    return _shortlist(scorer, shoemark_maps, shoeprint_maps, scores, k, locate, rotations, scales)
+    if not locate:
+        scores = scorer.score_matrix(shoemark_maps, shoeprint_maps, rotations=rotations, scales=scales)
+        return scores, _shortlist(scorer, shoemark_maps, shoeprint_maps, scores, k, False, rotations, scales)
+    scores, *located = scorer._score_matrix_located(shoemark_maps, shoeprint_maps, rotations, scales, fill_unfused=False)
+    return scores, _shortlist(scorer, shoemark_maps, shoeprint_maps, scores, k, True, rotations, scales, located=located)
 
 
 def _shortlist(scorer: NccScorer, shoemark_maps, shoeprint_maps, scores: np.ndarray, k: int, locate: bool, rotations,
-               scales) -> Shortlist:
+               scales, located=None) -> Shortlist:
     """``retrieve`` behind its score matrix: ``scores`` is what ``scorer.score_matrix`` gave for these maps and variants
-    (run_mi355x.py ranks from the same matrix instead of scoring twice)."""
+    (run_mi355x.py ranks from the same matrix instead of scoring twice).  ``located`` = the (variant, yx, t_hw) that
+    ``scorer._score_matrix_located`` gave beside ``scores``: the shortlisted entries are gathered from them, and only those
+    whose score is 0 - the scoring pass has no position for them - go through the second pass of ``NccScorer.locate``, which
+    gives the un-floored peak (without ``located``: all of them)."""
     dev = scorer.dev
     top_s, top_i = scorer.topk_device(dev.to_device(np.ascontiguousarray(scores, dtype=np.float32)), k)
     out = Shortlist(dev.to_host(top_i).astype(np.int32, copy=True), dev.to_host(top_s).astype(np.float32, copy=True),
@@ -603,8 +687,18 @@ def _shortlist(scorer: NccScorer, shoemark_maps, shoeprint_maps, scores: np.ndar
     qs, ps = np.nonzero(out.index >= 0)
     if len(qs) == 0:
         return out
-    _, variant, yx, t_hw = scorer._locate(shoemark_maps, shoeprint_maps, np.stack([qs, out.index[qs, ps]], axis=1),
-                                          rotations, scales)
+    gs = out.index[qs, ps]
+    if located is not None:
+        all_variant, all_yx, all_t_hw = located
+        variant, yx = all_variant[qs, gs], all_yx[qs, gs]
+        out.variant[qs, ps] = variant
+        out.peak_yx[qs, ps] = yx
+        out.offset[qs, ps] = yx - all_t_hw[qs, np.maximum(variant, 0)] // 2
+        rest = variant < 0
+        qs, ps, gs = qs[rest], ps[rest], gs[rest]
+        if len(qs) == 0:
+            return out
+    _, variant, yx, t_hw = scorer._locate(shoemark_maps, shoeprint_maps, np.stack([qs, gs], axis=1), rotations, scales)
     out.variant[qs, ps] = variant
     out.peak_yx[qs, ps] = yx
     out.offset[qs, ps] = yx - t_hw // 2
