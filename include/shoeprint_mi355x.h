@@ -304,15 +304,17 @@ int spr_vgg16_forward_taps(spr_vgg16_plan* plan, const uint8_t* images, int64_t 
                            void* workspace, float* out, int32_t n_taps, const int32_t* tap_convs, float* const* tap_out,
                            spr_stream_t stream);
 
-/* Per-layer trace of a 16-bit plan, for tests (the record format and the contract are spr_resnet_trace_layout's and
+/* Per-layer trace of a plan, for tests (the record format and the contract are spr_resnet_trace_layout's and
  * spr_resnet_forward_trace's, below): spr_vgg16_forward_trace is spr_vgg16_forward_taps - the same kernels, the same `out`,
  * the same taps - that also copies, behind every stage and on the same stream, what that stage stored into `trace`.  One
  * record per convolution of spr_vgg16_conv_shape's list, in that order:
- *   record 0                 the first convolution's output (bias, ReLU): 16-bit NHWC [n][h][w][64]
- *   record i, 0 < i < last   what stage i stored, behind bias / ReLU / the fused 2x2 max pool: 16-bit NHWC [n][h_i][w_i][cout_i]
+ *   record 0                 the first convolution's output (bias, ReLU): NHWC [n][h][w][64] in the plan's compute type
+ *   record i, 0 < i < last   what stage i stored, behind bias / ReLU / the fused 2x2 max pool: NHWC [n][h_i][w_i][cout_i] in
+ *                            the plan's compute type (float32 for a float32 plan)
  *   the last record          the float32 NCHW output [n][C][h][w], i.e. `out`
- * Refused with SPR_ERR_UNSUPPORTED by both entry points: float32 plans, and a 16-bit plan that consists of its first
- * convolution alone (it runs in float32, see spr_vgg_plan_create_ex, and stores no 16-bit record). */
+ * A float32 plan that is its first convolution alone has that one NCHW record.  Refused with SPR_ERR_UNSUPPORTED by both
+ * entry points: a 16-bit plan that consists of its first convolution alone (it runs in float32, see spr_vgg_plan_create_ex,
+ * and stores no 16-bit record).  SPR_ERR_SHAPE: the image vanishes under the pools. */
 int spr_vgg16_trace_layout(const spr_vgg16_plan* plan, int64_t n, int32_t in_h, int32_t in_w, int64_t* records,
                            size_t* total_bytes);
 int spr_vgg16_forward_trace(spr_vgg16_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
@@ -360,9 +362,9 @@ size_t spr_resnet_workspace_bytes(const spr_resnet_plan* plan, int64_t n, int32_
 int spr_resnet_forward(spr_resnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
                        int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
                        float* out, spr_stream_t stream);
-/* Per-layer trace of a 16-bit plan (f32 plans: SPR_ERR_UNSUPPORTED), for tests: spr_*_forward_trace is the plain forward
- * (the same kernels, the same result in `out`) that also copies, behind every layer and on the same stream, what that layer
- * stored into the device buffer `trace`.  spr_*_trace_layout(plan, n, in_h, in_w, records, total_bytes) returns the number of
+/* Per-layer trace of a plan of any compute type (a float32 plan stores float32 records), for tests: spr_*_forward_trace
+ * is the plain forward (the same kernels, the same result in `out`) that also copies, behind every layer and on the same
+ * stream, what that layer stored into the device buffer `trace`.  spr_*_trace_layout(plan, n, in_h, in_w, records, total_bytes) returns the number of
  * records and, where the pointers are not null, int64 records[6 * i ..] = byte offset into `trace`, h, w, channels, element
  * type (SPR_F16 | SPR_BF16 | SPR_F32), layout (0 NHWC: [n][h][w][channels], padded channels included; 1 NCHW: the float32
  * output of the last layer, real channels) and the size of `trace` in bytes.  ResNet records: the stem's output before the
@@ -408,8 +410,8 @@ int spr_effnet_forward(spr_effnet_plan* plan, const uint8_t* images, int64_t n, 
                        int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
                        float* out, spr_stream_t stream);
 /* Per-layer trace (see spr_resnet_forward_trace), one record per layer of the plan in order: the stem and every convolution /
- * depthwise convolution as stored (16-bit NHWC, cout_p channels), a squeeze-excitation's float32 factors [n][cin_p] (h = w =
- * 1), the last layer's float32 NCHW output. */
+ * depthwise convolution as stored (NHWC in the plan's compute type, cout_p channels), a squeeze-excitation's float32 factors
+ * [n][cin_p] (h = w = 1), the last layer's float32 NCHW output. */
 int spr_effnet_trace_layout(const spr_effnet_plan* plan, int64_t n, int32_t in_h, int32_t in_w, int64_t* records,
                             size_t* total_bytes);
 int spr_effnet_forward_trace(spr_effnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
@@ -453,7 +455,7 @@ size_t spr_densenet_workspace_bytes(const spr_densenet_plan* plan, int64_t n, in
 int spr_densenet_forward(spr_densenet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
                          int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
                          float* out, spr_stream_t stream);
-/* Per-layer trace of a 16-bit plan (see spr_resnet_forward_trace).  Records, all 16-bit NHWC but the last: the stem's output;
+/* Per-layer trace (see spr_resnet_forward_trace).  Records, all NHWC in the plan's compute type but the last: the stem's output;
  * block 1's tensor behind the max pool (its first 64 channels are written, the rest is whatever the workspace held); per
  * dense layer its 128-channel intermediate; per dense block its complete tensor behind the last layer (slices are never
  * overwritten: it holds every 3x3 result and every later layer's input); per transition its convolution's result and the

@@ -176,11 +176,13 @@ def operand16(x, scale, compute):
     return x if scale is None else _round(x * scale, compute)
 
 
-def se_step(op, p, x, dtype=torch.float32, bound=False):
+def se_step(op, p, x, dtype=torch.float32, bound=False, pool_chains=32):
     """Squeeze-excitation factors [N, C, 1, 1] of the stored tensor x: mean, fc1, SiLU, fc2, sigmoid, evaluated in ``dtype``.
     bound=True also returns E: an absolute bound on the float32 evaluation's error (the kernels' f32 chains, worst case:
     enet_pool16_kernel's 32 strided chains + their sum, enet_fc1_kernel's two fma chains + 7 adds, enet_fc2_kernel's four
-    chains + 3 adds; SiLU's slope <= 1.1, the sigmoid's <= 1/4, a few units of rounding for each of them)."""
+    chains + 3 adds; SiLU's slope <= 1.1, the sigmoid's <= 1/4, a few units of rounding for each of them).  pool_chains: the
+    strided chains the mean is summed in - 32 in enet_pool16_kernel, 4 in the float32 plans' enet_pool_kernel (x is then the
+    stored float32 tensor: nothing on this path is rounded to a 16-bit type)."""
     t = [torch.from_numpy(np.asarray(a, dtype=np.float32)).to(dtype) for a in p]
     x = x.to(dtype)
     with torch.no_grad():
@@ -192,7 +194,7 @@ def se_step(op, p, x, dtype=torch.float32, bound=False):
         u, hw, c, sq = 2.0 ** -24, x.shape[2] * x.shape[3], op["cin"], op["sq"]
         a = [v.abs() for v in t]
         pm = x.abs().mean(dim=(2, 3), keepdim=True)
-        e_p = (-(-hw // 32) + 34) * u * pm
+        e_p = (-(-hw // pool_chains) + 34) * u * pm
         mz = F.conv2d(pm, a[0].reshape(sq, c, 1, 1), a[1])
         e_z = (-(-c // 128) + 9) * u * mz + F.conv2d(e_p, a[0].reshape(sq, c, 1, 1))
         e_h = 1.1 * e_z + 4 * u * z.abs()

@@ -1,7 +1,7 @@
 // Internal declarations of the extractor side: the host launchers of the convolution kernels that the backbones share
 // (each kernel lives in one translation unit; other files reach it through its launcher) and the trace records of the
-// 16-bit plans (ResNet, EfficientNet, DenseNet, plain VGG).  All launchers enqueue on the stream and return SPR_OK /
-// SPR_ERR_HIP, or SPR_ERR_UNSUPPORTED for a kernel size / stride / tile combination that is not instantiated.
+// plans (ResNet, EfficientNet, DenseNet, plain VGG; float32 and 16-bit).  All launchers enqueue on the stream and return
+// SPR_OK / SPR_ERR_HIP, or SPR_ERR_UNSUPPORTED for a kernel size / stride / tile combination that is not instantiated.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -79,8 +79,9 @@ int check_forward_args(const char* name, const void* plan, const void* images, i
                        const float* mean3, const float* inv_std3, const void* packed, const void* workspace, const float* out);
 
 // ---- trace records (spr_*_forward_trace): what a layer stored, copied device to device behind it on the same stream.
-// Records lie 256-byte aligned in plan order; 16-bit NHWC [n][h][w][c] (c padded as stored), float32 [n][c] (squeeze-
-// excitation factors: h = w = 1) or the float32 NCHW output [n][c][h][w] of the last layer (c real).
+// Records lie 256-byte aligned in plan order; NHWC [n][h][w][c] in the plan's compute type (16-bit or float32; c padded as
+// stored), float32 [n][c] (squeeze-excitation factors: h = w = 1) or the float32 NCHW output [n][c][h][w] of the last layer
+// (c real).
 struct TraceRec { size_t off, bytes; int h, w, c, dtype, nchw; };
 struct TraceLayout {
   std::vector<TraceRec> recs;

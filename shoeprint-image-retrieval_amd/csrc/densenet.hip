@@ -456,16 +456,18 @@ int next_ld(const spr_densenet_plan* plan, size_t i, int fallback) {
   return i + 1 < plan->ops.size() && plan->ops[i + 1].kind == 1 ? plan->ops[i + 1].ctot : fallback;
 }
 
-// Records: the stem; block 1's tensor behind the max pool (channels [0, 64) written); per dense layer its 128-channel
-// intermediate; per dense block its complete tensor behind the last layer; per transition its convolution's result and the
-// next tensor behind the average pool (channels [0, cout) written); the float32 NCHW output.
+// Records (NHWC in the plan's compute type): the stem; block 1's tensor behind the max pool (channels [0, 64) written); per
+// dense layer its 128-channel intermediate; per dense block its complete tensor behind the last layer; per transition its
+// convolution's result and the next tensor behind the average pool (channels [0, cout) written); the float32 NCHW output.
 TraceLayout densenet_trace_layout(const spr_densenet_plan* plan, int64_t n, int in_h, int in_w) {
   TraceLayout lay;
   lay.n = n;
   int h = (in_h + 1) / 2, w = (in_w + 1) / 2, c = 64;
   lay.add(h, w, 64, plan->compute, 0);
-  h = (h + 1) / 2; w = (w + 1) / 2;
-  lay.add(h, w, next_ld(plan, 0, 64), plan->compute, 0);
+  if (plan->ops[0].flags & 4) {  // (an f32 plan may end in front of the max pool)
+    h = (h + 1) / 2; w = (w + 1) / 2;
+    lay.add(h, w, next_ld(plan, 0, 64), plan->compute, 0);
+  }
   for (size_t i = 1; i < plan->ops.size(); ++i) {
     const DOp& o = plan->ops[i];
     if (o.kind == 1) lay.add(h, w, 128, plan->compute, 0);
@@ -484,8 +486,8 @@ TraceLayout densenet_trace_layout(const spr_densenet_plan* plan, int64_t n, int 
 }
 }  // namespace
 
-// The forward pass of both compute types: one walk over the plan, tensors in the plan's type.  trace: null (always for an f32
-// plan), or where the records of densenet_trace_layout are copied
+// The forward pass of both compute types: one walk over the plan, tensors in the plan's type.  trace: null (the plain
+// forward), or where the records of densenet_trace_layout are copied
 static int densenet_forward(spr_densenet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
                             int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
                             float* out, spr_stream_t stream, unsigned char* trace) {
@@ -592,7 +594,6 @@ extern "C" int spr_densenet_forward(spr_densenet_plan* plan, const uint8_t* imag
 extern "C" int spr_densenet_trace_layout(const spr_densenet_plan* plan, int64_t n, int32_t in_h, int32_t in_w, int64_t* records,
                                          size_t* total_bytes) {
   if (!plan || n < 0 || in_h < 32 || in_w < 32) { set_error("spr_densenet_trace_layout: bad argument"); return SPR_ERR_ARG; }
-  if (plan->compute == SPR_F32) { set_error("spr_densenet_trace_layout: 16-bit plans only"); return SPR_ERR_UNSUPPORTED; }
   return trace_query(densenet_trace_layout(plan, n, in_h, in_w), records, total_bytes);
 }
 
@@ -600,7 +601,6 @@ extern "C" int spr_densenet_forward_trace(spr_densenet_plan* plan, const uint8_t
                                           int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
                                           void* workspace, float* out, void* trace, spr_stream_t stream) {
   if (!plan || !trace) { set_error("spr_densenet_forward_trace: null pointer"); return SPR_ERR_ARG; }
-  if (plan->compute == SPR_F32) { set_error("spr_densenet_forward_trace: 16-bit plans only"); return SPR_ERR_UNSUPPORTED; }
   return densenet_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, stream,
                           static_cast<unsigned char*>(trace));
 }

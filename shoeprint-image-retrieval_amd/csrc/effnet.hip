@@ -407,8 +407,8 @@ extern "C" size_t spr_effnet_workspace_bytes(const spr_effnet_plan* plan, int64_
          align_up(static_cast<size_t>(n) * plan->max_sq * sizeof(float), 256);
 }
 
-// one record per layer in plan order: the stem and every convolution / depthwise convolution as stored (16-bit NHWC, cout_p
-// channels), a squeeze-excitation's float32 factors [n][cin_p], the last layer's float32 NCHW output
+// one record per layer in plan order: the stem and every convolution / depthwise convolution as stored (NHWC in the plan's
+// compute type, cout_p channels), a squeeze-excitation's float32 factors [n][cin_p], the last layer's float32 NCHW output
 static TraceLayout effnet_trace_layout(const spr_effnet_plan* plan, int64_t n, int in_h, int in_w) {
   TraceLayout lay;
   lay.n = n;
@@ -426,7 +426,6 @@ static TraceLayout effnet_trace_layout(const spr_effnet_plan* plan, int64_t n, i
 extern "C" int spr_effnet_trace_layout(const spr_effnet_plan* plan, int64_t n, int32_t in_h, int32_t in_w, int64_t* records,
                                        size_t* total_bytes) {
   if (!plan || n < 0 || in_h < 32 || in_w < 32) { set_error("spr_effnet_trace_layout: bad argument"); return SPR_ERR_ARG; }
-  if (plan->compute == SPR_F32) { set_error("spr_effnet_trace_layout: 16-bit plans only"); return SPR_ERR_UNSUPPORTED; }
   return trace_query(effnet_trace_layout(plan, n, in_h, in_w), records, total_bytes);
 }
 
@@ -435,7 +434,7 @@ extern "C" int spr_effnet_trace_layout(const spr_effnet_plan* plan, int64_t n, i
 // stem as an ordinary one with 16 input channels) on conv_gemm_kernel.  16-bit: the stem on stem16_kernel's 3x3 / stride 2
 // instance, every other convolution on conv_gemm16_kernel.  Both: SiLU in front of the residual sum, squeeze-excitation
 // factors on the operand, depthwise convolutions and the squeeze-excitation mean on their kernels per type; float32 NCHW out.
-// trace: null (always for an f32 plan), or where every layer's stored result is copied (effnet_trace_layout)
+// trace: null (the plain forward), or where every layer's stored result is copied (effnet_trace_layout)
 static int effnet_forward(const spr_effnet_plan* plan, const uint8_t* images, int64_t n, int in_h, int in_w, int in_channels,
                           const float* mean3, const float* inv_std3, const void* packed, void* workspace, float* out,
                           spr_stream_t stream, unsigned char* trace) {
@@ -542,7 +541,6 @@ extern "C" int spr_effnet_forward_trace(spr_effnet_plan* plan, const uint8_t* im
                                         int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
                                         void* workspace, float* out, void* trace, spr_stream_t stream) {
   if (!plan || !trace) { set_error("spr_effnet_forward_trace: null pointer"); return SPR_ERR_ARG; }
-  if (plan->compute == SPR_F32) { set_error("spr_effnet_forward_trace: 16-bit plans only"); return SPR_ERR_UNSUPPORTED; }
   return effnet_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, stream,
                         static_cast<unsigned char*>(trace));
 }

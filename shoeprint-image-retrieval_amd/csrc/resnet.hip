@@ -154,17 +154,24 @@ extern "C" int spr_resnet_pack_weights(spr_resnet_plan* plan, const float* const
 }
 
 // four activation buffers (block input, two bottleneck intermediates / the downsample branch, block output), each as
-// large as the largest tensor between layers: the stem's output
+// large as the largest tensor between layers
 static size_t resnet_big16_bytes(int64_t n, int in_h, int in_w) {  // layer1's output, the largest 16-bit tensor
   const int hp = ((in_h + 1) / 2 + 1) / 2, wp = ((in_w + 1) / 2 + 1) / 2;
   return align_up(static_cast<size_t>(n) * hp * wp * 256 * sizeof(uint16_t), 256);
+}
+// one of the four activation buffers of an f32 plan: the stem's output or layer1's, whichever is larger (the max pool rounds
+// odd sizes up, so 256 channels on the pooled map can outgrow 64 channels on the stem's: 17 x 24 -> 9 x 12)
+static size_t resnet_buf32_bytes(int64_t n, int in_h, int in_w) {
+  const int hs = (in_h + 1) / 2, ws = (in_w + 1) / 2;
+  const size_t stem = static_cast<size_t>(n) * hs * ws * 64, layer1 = static_cast<size_t>(n) * ((hs + 1) / 2) * ((ws + 1) / 2) * 256;
+  return align_up(std::max(stem, layer1) * sizeof(float), 256);
 }
 extern "C" size_t spr_resnet_workspace_bytes(const spr_resnet_plan* plan, int64_t n, int32_t in_h, int32_t in_w) {
   if (!plan || n < 0) return 0;
   const size_t stem = static_cast<size_t>(n) * ((in_h + 1) / 2) * ((in_w + 1) / 2) * 64;
   // 16-bit plans: the stem's f32 tensor, then four 16-bit activation buffers
   if (plan->compute != SPR_F32) return align_up(stem * sizeof(float), 256) + 4 * resnet_big16_bytes(n, in_h, in_w);
-  return 4 * align_up(stem * sizeof(float), 256);
+  return 4 * resnet_buf32_bytes(n, in_h, in_w);
 }
 
 // one convolution of the plan: conv_gemm_kernel for an f32 plan; in a 16-bit plan vgg_conv.hip's patch kernel for the 3x3 /
@@ -207,11 +214,10 @@ static TraceLayout resnet_trace_layout(const spr_resnet_plan* plan, int64_t n, i
 extern "C" int spr_resnet_trace_layout(const spr_resnet_plan* plan, int64_t n, int32_t in_h, int32_t in_w, int64_t* records,
                                        size_t* total_bytes) {
   if (!plan || n < 0 || in_h < 32 || in_w < 32) { set_error("spr_resnet_trace_layout: bad argument"); return SPR_ERR_ARG; }
-  if (plan->compute == SPR_F32) { set_error("spr_resnet_trace_layout: 16-bit plans only"); return SPR_ERR_UNSUPPORTED; }
   return trace_query(resnet_trace_layout(plan, n, in_h, in_w), records, total_bytes);
 }
 
-// trace: null (the plain forward; always for an f32 plan), or where the stem's, the max pool's and every convolution's stored
+// trace: null (the plain forward), or where the stem's, the max pool's and every convolution's stored
 // result is copied (resnet_trace_layout: record 1 + conv index)
 static int resnet_forward(spr_resnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
                           int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
@@ -225,7 +231,7 @@ static int resnet_forward(spr_resnet_plan* plan, const uint8_t* images, int64_t 
   // f32: four buffers, the stem's output in the second.  16-bit: [stem's tensor][x][t1][t2][y]
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   const size_t stem_bytes = align_up(static_cast<size_t>(n) * ((in_h + 1) / 2) * ((in_w + 1) / 2) * 64 * sizeof(float), 256);
-  const size_t first = f32 ? 0 : stem_bytes, step = f32 ? stem_bytes : resnet_big16_bytes(n, in_h, in_w);
+  const size_t first = f32 ? 0 : stem_bytes, step = f32 ? resnet_buf32_bytes(n, in_h, in_w) : resnet_big16_bytes(n, in_h, in_w);
   void* x = ws + first;             // block input (first: the pooled stem output)
   void* t1 = ws + first + step;     // conv1's output, then the downsample branch's
   void* t2 = ws + first + 2 * step;
@@ -291,7 +297,6 @@ extern "C" int spr_resnet_forward_trace(spr_resnet_plan* plan, const uint8_t* im
                                         int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
                                         void* workspace, float* out, void* trace, spr_stream_t stream) {
   if (!plan || !trace) { set_error("spr_resnet_forward_trace: null pointer"); return SPR_ERR_ARG; }
-  if (plan->compute == SPR_F32) { set_error("spr_resnet_forward_trace: 16-bit plans only"); return SPR_ERR_UNSUPPORTED; }
   return resnet_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, stream,
                         static_cast<unsigned char*>(trace));
 }

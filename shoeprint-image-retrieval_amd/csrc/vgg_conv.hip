@@ -721,8 +721,8 @@ extern "C" size_t spr_vgg16_workspace_bytes(const spr_vgg16_plan* plan, int64_t 
   return 2 * align_up(biggest * (plan->compute == SPR_F32 ? sizeof(float) : sizeof(uint16_t)), 256);
 }
 
-// Trace records of a 16-bit plan (spr_vgg16_trace_layout): what every stage stored, behind bias / ReLU / pool - 16-bit NHWC
-// for the stem and every stage but the last, the float32 NCHW output for the last.
+// Trace records (spr_vgg16_trace_layout): what every stage stored, behind bias / ReLU / pool - NHWC in the plan's compute
+// type for the stem and every stage but the last, the float32 NCHW output for the last.
 static TraceLayout vgg_trace_layout(const spr_vgg16_plan* plan, int64_t n, int in_h, int in_w) {
   TraceLayout lay;
   lay.n = n;
@@ -736,10 +736,9 @@ static TraceLayout vgg_trace_layout(const spr_vgg16_plan* plan, int64_t n, int i
   return lay;
 }
 
-// A 16-bit plan with stages behind its first convolution; anything else has no trace.
+// Every float32 plan traces; a 16-bit plan needs stages behind its first convolution.
 static int vgg_trace_refusal(const spr_vgg16_plan* plan, const char* who) {
-  if (plan->compute == SPR_F32) { set_error("%s: 16-bit plans only", who); return SPR_ERR_UNSUPPORTED; }
-  if (plan->stages.size() < 2) {
+  if (plan->compute != SPR_F32 && plan->stages.size() < 2) {
     set_error("%s: a plan that is its first convolution alone runs in float32 and stores no 16-bit record", who);
     return SPR_ERR_UNSUPPORTED;
   }

@@ -419,7 +419,7 @@ def check_batch_invariance(block, hw, compute, device, lib):
 
 
 def check_surface(device, lib):
-    """The plan's compute codes, the refusals, and _ex(block, 0) against spr_densenet_plan_create."""
+    """The plan's compute codes, the refusals, a float32 plan's trace layout, and _ex(block, 0) against spr_densenet_plan_create."""
     from shoeprint_image_retrieval_amd import network
 
     for compute, code in (("bfloat16", 2), ("float16", 1)):
@@ -445,12 +445,20 @@ def check_surface(device, lib):
             assert network.densenet_plan_ops(lib, a) == network.densenet_plan_ops(lib, b)
             assert lib.spr_densenet_packed_bytes(a) == lib.spr_densenet_packed_bytes(b)
             assert lib.spr_densenet_workspace_bytes(a, 2, 40, 36) == lib.spr_densenet_workspace_bytes(b, 2, 40, 36)
+            # a float32 plan traces: SPR_OK, the same records from both constructors, and (through a Model of that block) the
+            # expected count, every record's (h, w, c, dtype, nchw) and total_bytes = the sum of the 256-aligned records
+            import f32_layer_cases as fc
+
+            assert lc.trace_records(lib.spr_densenet_trace_layout, a, 1, 40, 40) == lc.trace_records(lib.spr_densenet_trace_layout, b, 1, 40, 40)
+            m = lc.make_model(ARCH, block, "float32", device, lib)
+            try:
+                assert fc.check_layout(m, lib, 1, (40, 40)) == lc.trace_records(lib.spr_densenet_trace_layout, b, 1, 40, 40)[0]
+            finally:
+                m.close()
             total = C.c_size_t(0)
-            assert lib.spr_densenet_trace_layout(b, 1, 40, 40, None, C.byref(total)) == -3  # SPR_ERR_UNSUPPORTED
-            dummy = device.to_device(np.zeros(64, np.uint8))
-            assert lib.spr_densenet_forward_trace(b, device.ptr(dummy), 1, 40, 40, 1, (C.c_float * 3)(), (C.c_float * 3)(),
-                                                  device.ptr(dummy), device.ptr(dummy), device.ptr(dummy), device.ptr(dummy),
-                                                  device.stream()) == -3
+            assert lib.spr_densenet_trace_layout(b, 1, 16, 40, None, C.byref(total)) == -1  # SPR_ERR_ARG: at least 32 x 32
+            assert lib.spr_densenet_forward_trace(b, None, 1, 40, 40, 1, (C.c_float * 3)(), (C.c_float * 3)(), None, None, None, None,
+                                                  device.stream()) == -1              # a null trace
         finally:
             lib.spr_densenet_plan_destroy(a)
             lib.spr_densenet_plan_destroy(b)

@@ -39,7 +39,9 @@ def test_emu_per_layer_parity_resnet_wide_tiles():
     assert "1 passed" in r.stdout, r.stdout[-2000:]
 
 
-def test_emu_trace_entry_points_refuse_f32_plans():
+def test_emu_trace_layouts_of_f32_plans_and_argument_refusals():
+    import f32_layer_cases as fc
+
     lib = emu_library()
     m = lc.make_model("EfficientNetV2_S", 3, "bfloat16", HostDevice(), lib)
     m32 = lc.make_model("ResNet50", 5, "float32", HostDevice(), lib)
@@ -47,7 +49,9 @@ def test_emu_trace_entry_points_refuse_f32_plans():
         import ctypes as C
 
         total = C.c_size_t(0)
-        assert lib.spr_resnet_trace_layout(m32.handle, 1, 40, 40, None, C.byref(total)) == -3  # SPR_ERR_UNSUPPORTED
+        # a float32 plan traces: SPR_OK, the expected records (float32 NHWC, the last NCHW), total_bytes their aligned sum
+        assert len(fc.check_layout(m32, lib, 1, (40, 40))) == 1 + len(m32.conv_specs())
+        assert lib.spr_resnet_trace_layout(m32.handle, 1, 40, 16, None, C.byref(total)) == -1  # SPR_ERR_ARG: at least 32 x 32
         assert lib.spr_effnet_trace_layout(m.handle, 1, 16, 40, None, C.byref(total)) == -1  # SPR_ERR_ARG: at least 32 x 32
         assert lib.spr_effnet_trace_layout(m.handle, 1, 40, 40, None, C.byref(total)) == len(m.effnet_ops()) and total.value > 0
     finally:

@@ -322,12 +322,16 @@ def check_get_feature_maps(arch, block, hw, compute, device, lib) -> str:
 
 
 def check_refusals(device, lib):
-    """Float32 plans and a 16-bit plan that is its first convolution alone (it runs conv_first_kernel in float32): both trace
-    entry points answer SPR_ERR_UNSUPPORTED and write nothing; an image that vanishes under the pools: SPR_ERR_SHAPE."""
+    """A 16-bit plan that is its first convolution alone (it runs conv_first_kernel in float32 and stores no 16-bit record): both
+    trace entry points answer SPR_ERR_UNSUPPORTED and write nothing.  Float32 plans trace (tests/f32_layer_cases.py): the layout
+    is SPR_OK with the expected record count, every record's (h, w, c, dtype, nchw) and total_bytes = the sum of the 256-aligned
+    records - a plan that is its first convolution alone included: one float32 NCHW record.  An image that vanishes under the
+    pools: SPR_ERR_SHAPE, in either compute type."""
+    import f32_layer_cases as fc
+
     dummy = device.to_device(np.zeros(4096, np.uint8))
     p, f3 = device.ptr(dummy), (C.c_float * 3)()
-    for arch, block, compute in (("VGG16", 10, "float32"), ("VGG19_BN", 9, "float32"), ("VGG16", 2, "bfloat16"),
-                                 ("VGG19_BN", 3, "float16")):
+    for arch, block, compute in (("VGG16", 2, "bfloat16"), ("VGG19_BN", 3, "float16")):
         m = lc.make_model(arch, block, compute, device, lib)
         try:
             total = C.c_size_t(77)
@@ -337,6 +341,18 @@ def check_refusals(device, lib):
                                                device.stream()) == UNSUPPORTED, (arch, block, compute)
             device.synchronize()
             assert not np.asarray(device.to_host(dummy)).any()
+        finally:
+            m.close()
+    for arch, block, count in (("VGG16", 10, 4), ("VGG19_BN", 9, 3), ("VGG16", 2, 1), ("VGG19_BN", 3, 1)):
+        m = lc.make_model(arch, block, "float32", device, lib)
+        try:
+            for n, hw in ((1, (40, 40)), (3, (37, 51))):
+                assert len(fc.check_layout(m, lib, n, hw)) == count, (arch, block)
+            total = C.c_size_t(0)
+            if count > 2:
+                assert lib.spr_vgg16_trace_layout(m.handle, 1, 1, 40, None, C.byref(total)) == -2   # SPR_ERR_SHAPE
+            assert lib.spr_vgg16_trace_layout(m.handle, 1, 0, 40, None, C.byref(total)) == -1       # SPR_ERR_ARG
+            assert lib.spr_vgg16_forward_trace(m.handle, p, 1, 8, 8, 1, f3, f3, p, p, p, 0, None, None, None, device.stream()) == -1
         finally:
             m.close()
     m = lc.make_model("VGG16", 10, "bfloat16", device, lib)
