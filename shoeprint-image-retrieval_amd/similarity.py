@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Any, Sequence
+from typing import Any, NamedTuple, Sequence
 
 import numpy as np
 
@@ -86,6 +86,12 @@ def _as_item_list(maps) -> tuple[list | None, Any]:
     if isinstance(maps, (list, tuple)):
         return list(maps), None
     return None, maps
+
+
+def _host_items(dev, maps) -> list:
+    """List of per-item host arrays of any accepted input (a device batch is copied to the host)."""
+    items, batch = _as_item_list(maps)
+    return list(dev.to_host(batch)) if items is None else items
 
 
 class NccScorer:
@@ -198,18 +204,16 @@ class NccScorer:
         ng, c2, gh, gw = self.dev.shape(g_dev)
         if c != c2:
             raise ValueError(f"channel mismatch: queries {c}, gallery {c2}")
+        if plan is None and str(q_dev.dtype) != str(g_dev.dtype):
+            raise ValueError(f"storage type mismatch: queries {q_dev.dtype}, gallery {g_dev.dtype}")
         if plan is None and scores is None and not accumulate_max and self._torch_ops() is not None:
             # north_star's named mechanism: the registered PyTorch-ROCm custom op (csrc/torch_ops.cpp), same entry points
-            if str(q_dev.dtype) != str(g_dev.dtype):
-                raise ValueError(f"storage type mismatch: queries {q_dev.dtype}, gallery {g_dev.dtype}")
             method = self.method
             if self.f32_matrix_cores:  # the op resolves a method name by itself: hand it the one this scorer's plan took
                 if self.plan(c, (qh, qw), (gh, gw), dtype=q_dev.dtype).method == _lib.NCC_MFMA_F32:
                     method = _lib.NCC_MFMA_F32
             return self._torch_ops().ncc_scores(q_dev, g_dev, self.crop, _lib.METHOD_NAMES[method], self._budget())
         if plan is None:
-            if str(q_dev.dtype) != str(g_dev.dtype):
-                raise ValueError(f"storage type mismatch: queries {q_dev.dtype}, gallery {g_dev.dtype}")
             plan = self.plan(c, (qh, qw), (gh, gw), dtype=q_dev.dtype)
         if scores is None:
             scores = self.dev.zeros((nq, ng), np.float32)
@@ -305,26 +309,62 @@ class NccScorer:
         return score, yx
 
     # ------------------------------------------------------------------ list-of-arrays level
+    def _blocks(self, q_items, g_items, rotations, scales, q_used=None, g_used=None):
+        """THE walk over ragged host item lists, behind ``score_matrix``, ``score_matrix_located`` and ``locate``: grouping by
+        shape, variant lists, plans, chunk budget and gallery preparation are decided here and nowhere else.  Of the items
+        ``q_used`` / ``g_used`` (ascending indices; default all) every query shape class is stacked, uploaded, expanded by
+        ``VariantBuilder.variants`` and cast to the storage type once; every gallery shape class gets one plan per distinct
+        variant shape (the 1/sigma map depends on the template size) and goes chunk by chunk, the prepared forms of a chunk -
+        one per plan, all alive while the query classes are walked - sharing the budget.  Yields per (gallery chunk, query
+        class) a ``_Block``; its ``prepared(vs)`` uploads the chunk on first need and prepares it once per variant shape, so a
+        block the consumer passes over costs nothing.  A block is good until the walk is advanced."""
+        from .variants import VariantBuilder
+
+        if self._variants is None:
+            self._variants = VariantBuilder(self.lib, self.dev)  # (keeps its resample tables on the device)
+        q_side = []
+        for qshape, q_idx in _group_by_shape(q_items, q_used).items():
+            batches = self._variants.variants(self.dev.stack_to_device([q_items[i] for i in q_idx]), rotations, scales)
+            q_side.append((qshape, q_idx, [(number, tuple(self.dev.shape(v)[2:]), self.dev.astype_storage(v, self.storage))
+                                           for number, v in enumerate(batches)]))
+        for gshape, g_idx in _group_by_shape(g_items, g_used).items():
+            plans = {}
+            for qshape, _, variants in q_side:
+                if qshape[0] != gshape[0]:
+                    raise ValueError(f"channel mismatch: query {qshape}, gallery {gshape}")
+                for _, vs, _ in variants:
+                    plans[vs] = self.plan(qshape[0], vs, gshape[1:], dtype=self.storage)
+            chunk = min(self.gallery_chunk_items(p, len(g_idx), share=len(plans)) for p in plans.values())
+            for start in range(0, len(g_idx), chunk):
+                idx = g_idx[start:start + chunk]
+                alive = {}  # None -> the uploaded chunk, variant shape -> its prepared form
+
+                def prepared(vs):
+                    if vs not in alive:
+                        if None not in alive:
+                            alive[None] = self.dev.astype_storage(self.dev.stack_to_device([g_items[i] for i in idx]),
+                                                                  self.storage)
+                        alive[vs] = self.prepare_gallery(plans[vs], alive[None])
+                    return alive[vs]
+
+                for _, q_idx, variants in q_side:
+                    yield _Block(q_idx, variants, idx, plans, chunk, prepared)
+
     def locate(self, shoemark_maps, shoeprint_maps, pairs, rotations=None, scales=None):
         """Where and under which variant every pair of ``pairs`` = [(query index, gallery index), ...] matches best:
         host arrays (score float32 [P], variant int32 [P], yx int32 [P,2]).  Per pair and per variant list - numbered in
         the order of ``VariantBuilder.variants``, 0 = the query as it is - the channel-summed NCC map is reduced to its
         peak (first maximum in row-major order, cropped search-map coordinates); the variant with the largest peak wins,
         the lowest number among equal peaks.  ``score`` is that peak over the channel count: get_similarity's value,
-        NOT floored at 0.  A second pass beside the pair kernels, which keep only the maximum: the union of the gallery
-        items the pairs name is uploaded once and prepared once per plan, ragged sets go by shape class as in
-        ``score_matrix``."""
+        NOT floored at 0.  A second pass beside the pair kernels, which keep only the maximum: ``score_matrix``'s walk
+        (``_blocks``) over the items the pairs name, so the union of those gallery items is uploaded once and prepared once
+        per plan, and blocks that hold no pair are passed over."""
         return self._locate(shoemark_maps, shoeprint_maps, pairs, rotations, scales)[:3]
 
     def _locate(self, shoemark_maps, shoeprint_maps, pairs, rotations, scales):
         """``locate`` plus the cropped size (th, tw) int32 [P,2] of every pair's winning variant template, read off the
         variant batches themselves."""
-        q_items, q_dev = _as_item_list(shoemark_maps)
-        g_items, g_dev = _as_item_list(shoeprint_maps)
-        if q_items is None:
-            q_items = list(self.dev.to_host(q_dev))
-        if g_items is None:
-            g_items = list(self.dev.to_host(g_dev))
+        q_items, g_items = _host_items(self.dev, shoemark_maps), _host_items(self.dev, shoeprint_maps)
         pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
         n = len(pairs)
         best = np.full(n, -np.inf, dtype=np.float32)
@@ -335,49 +375,22 @@ class NccScorer:
             return best, variant, yx, t_hw
         if pairs.min() < 0 or pairs[:, 0].max() >= len(q_items) or pairs[:, 1].max() >= len(g_items):
             raise IndexError("a pair names an item outside the query or gallery set")
-        q_used = sorted({int(q) for q in pairs[:, 0]})
-        g_used = sorted({int(g) for g in pairs[:, 1]})
-        q_groups = {shape: [q_used[i] for i in idx] for shape, idx in _group_by_shape([q_items[q] for q in q_used]).items()}
-        g_groups = {shape: [g_used[i] for i in idx] for shape, idx in _group_by_shape([g_items[g] for g in g_used]).items()}
-        from .variants import VariantBuilder
-
-        if self._variants is None:
-            self._variants = VariantBuilder(self.lib, self.dev)
-        q_side, q_pos = {}, {}
-        for qshape, q_idx in q_groups.items():
-            q_batch = self.dev.stack_to_device([q_items[i] for i in q_idx])
-            q_side[qshape] = [(tuple(self.dev.shape(v)[2:]), self.dev.astype_storage(v, self.storage))
-                              for v in self._variants.variants(q_batch, rotations, scales)]
-            q_pos[qshape] = {q: i for i, q in enumerate(q_idx)}
-        for gshape, g_idx in g_groups.items():
-            plans = {}
-            for qshape, vlist in q_side.items():
-                if qshape[0] != gshape[0]:
-                    raise ValueError(f"channel mismatch: query {qshape}, gallery {gshape}")
-                for vs, _ in vlist:
-                    plans[vs] = self.plan(qshape[0], vs, gshape[1:], dtype=self.storage)
-            chunk = min(self.gallery_chunk_items(p, len(g_idx), share=len(plans)) for p in plans.values())
-            for start in range(0, len(g_idx), chunk):
-                idx = g_idx[start:start + chunk]
-                g_pos = {g: i for i, g in enumerate(idx)}
-                g_batch = None
-                prepared = {}  # variant shape -> prepared gallery chunk
-                for qshape, vlist in q_side.items():
-                    sel = [i for i in range(n) if int(pairs[i, 0]) in q_pos[qshape] and int(pairs[i, 1]) in g_pos]
-                    if not sel:
-                        continue
-                    slots = [(q_pos[qshape][int(pairs[i, 0])], g_pos[int(pairs[i, 1])]) for i in sel]
-                    if g_batch is None:
-                        g_batch = self.dev.astype_storage(self.dev.stack_to_device([g_items[i] for i in idx]), self.storage)
-                    for number, (vs, v) in enumerate(vlist):
-                        plan = plans[vs]
-                        if vs not in prepared:
-                            prepared[vs] = self.prepare_gallery(plan, g_batch)
-                        score, pos = self.peaks_device(plan, self.prepare_queries(plan, v), prepared[vs], slots)
-                        better = score > best[sel]  # strictly: the lowest variant number keeps an equal peak
-                        rows = np.asarray(sel)[better]
-                        best[rows], variant[rows], yx[rows] = score[better], number, pos[better]
-                        t_hw[rows] = (vs[0] - 2 * self.crop, vs[1] - 2 * self.crop)
+        q_used, g_used = (sorted({int(i) for i in pairs[:, side]}) for side in (0, 1))
+        for b in self._blocks(q_items, g_items, rotations, scales, q_used, g_used):
+            q_pos = {q: i for i, q in enumerate(b.q_idx)}
+            g_pos = {g: i for i, g in enumerate(b.g_idx)}
+            sel = [i for i in range(n) if int(pairs[i, 0]) in q_pos and int(pairs[i, 1]) in g_pos]
+            if not sel:
+                continue
+            slots = [(q_pos[int(pairs[i, 0])], g_pos[int(pairs[i, 1])]) for i in sel]
+            for number, vs, v in b.variants:
+                plan = b.plans[vs]
+                pg = b.prepared(vs)
+                score, pos = self.peaks_device(plan, self.prepare_queries(plan, v), pg, slots)
+                better = score > best[sel]  # strictly: the lowest variant number keeps an equal peak
+                rows = np.asarray(sel)[better]
+                best[rows], variant[rows], yx[rows] = score[better], number, pos[better]
+                t_hw[rows] = (vs[0] - 2 * self.crop, vs[1] - 2 * self.crop)
         return best, variant, yx, t_hw
 
     def score_matrix(self, shoemark_maps, shoeprint_maps, accumulate_into=None, rotations=None,
@@ -390,38 +403,33 @@ class NccScorer:
         q_items, q_dev = _as_item_list(shoemark_maps)
         g_items, g_dev = _as_item_list(shoeprint_maps)
         if q_items is None and g_items is None and rotations is None and scales is None:
-            scores = self.scores_device(q_dev, g_dev)
-            return self.dev.to_host(scores)
-        return self._walk(q_items, q_dev, g_items, g_dev, accumulate_into, rotations, scales, False)[0]
+            return self.dev.to_host(self.scores_device(q_dev, g_dev))
+        return self._walk(shoemark_maps, shoeprint_maps, accumulate_into, rotations, scales, False)[0]
 
     def score_matrix_located(self, shoemark_maps, shoeprint_maps, rotations=None, scales=None):
         """``score_matrix`` with, for every pair, the variant that gave its score and where that variant's NCC map peaks:
         host ``(scores float32 [Q,G], variant int32 [Q,G], yx int32 [Q,G,2])``, out of the scoring pass itself
-        (spr_ncc_score_peaks) - same grouping by shape, variant lists (numbered as ``VariantBuilder.variants`` /
-        ``variant_labels``), gallery chunks and budget sharing, and bit for bit the same ``scores``.  ``yx`` is in cropped
-        search-map coordinates; the lowest variant number wins among equal scores.  A pair whose score is 0 (no variant's
-        map rises above 0) has variant -1 and yx (-1, -1).  The arg-max is taken on the kernels' float32 channel sums,
-        ``locate`` sums the per-channel maps in float64: the two may name different pixels where the two largest sums lie
-        within rounding of each other.  Plans without a peak form (the matrix-core methods) are scored as ever and their
-        blocks located by the second pass of ``locate``."""
+        (spr_ncc_score_peaks) - the same walk (``_blocks``), hence the same grouping by shape, variant lists (numbered as
+        ``VariantBuilder.variants`` / ``variant_labels``), gallery chunks and budget sharing, and bit for bit the same
+        ``scores``.  ``yx`` is in cropped search-map coordinates; the lowest variant number wins among equal scores.  A pair
+        whose score is 0 (no variant's map rises above 0) has variant -1 and yx (-1, -1).  The arg-max is taken on the
+        kernels' float32 channel sums, ``locate`` sums the per-channel maps in float64: the two may name different pixels where
+        the two largest sums lie within rounding of each other.  Plans without a peak form (the matrix-core methods) are
+        scored as ever and their blocks located by the second pass of ``locate``."""
         return self._score_matrix_located(shoemark_maps, shoeprint_maps, rotations, scales)[:3]
 
     def _score_matrix_located(self, shoemark_maps, shoeprint_maps, rotations, scales, fill_unfused: bool = True):
         """``score_matrix_located`` plus the cropped template size (th, tw) int32 [Q,V,2] of every query's variants.
         ``fill_unfused`` False leaves the blocks of plans without a peak form at variant -1 / yx (-1, -1) instead of
         running the second pass over ALL their pairs: ``retrieve`` locates only the pairs it shortlists."""
-        q_items, q_dev = _as_item_list(shoemark_maps)
-        g_items, g_dev = _as_item_list(shoeprint_maps)
-        return self._walk(q_items, q_dev, g_items, g_dev, None, rotations, scales, True, fill_unfused)
+        return self._walk(shoemark_maps, shoeprint_maps, None, rotations, scales, True, fill_unfused)
 
-    def _walk(self, q_items, q_dev, g_items, g_dev, accumulate_into, rotations, scales, located: bool,
+    def _walk(self, shoemark_maps, shoeprint_maps, accumulate_into, rotations, scales, located: bool,
               fill_unfused: bool = True):
-        """The list-of-arrays scoring walk behind ``score_matrix`` (``located`` False: plain spr_ncc_score launches, the
-        last three results are None) and ``score_matrix_located``: (scores, variant, yx, t_hw)."""
-        if q_items is None:
-            q_items = list(self.dev.to_host(q_dev))
-        if g_items is None:
-            g_items = list(self.dev.to_host(g_dev))
+        """The scoring consumer of ``_blocks`` behind ``score_matrix`` (``located`` False: plain spr_ncc_score launches, the
+        last three results are None) and ``score_matrix_located``: (scores, variant, yx, t_hw).  Every block is scored into a
+        device matrix of its own, all variants in ascending number through accumulate_max, and folded into the host matrix."""
+        q_items, g_items = _host_items(self.dev, shoemark_maps), _host_items(self.dev, shoeprint_maps)
         nq, ng = len(q_items), len(g_items)
         out = np.zeros((nq, ng), dtype=np.float32) if accumulate_into is None else accumulate_into
         variant = yx = t_hw = None
@@ -434,64 +442,30 @@ class NccScorer:
             second_pass = []  # blocks (query indices, gallery indices) one of whose plans has no peak form
         if nq == 0 or ng == 0:
             return out, variant, yx, t_hw
-        q_groups = _group_by_shape(q_items)
-        g_groups = _group_by_shape(g_items)
-        from .variants import VariantBuilder
-
-        if self._variants is None:
-            self._variants = VariantBuilder(self.lib, self.dev)  # (keeps its resample tables on the device)
-        builder = self._variants
-        # Every query shape group is uploaded and expanded into its variant list ONCE; every gallery chunk is uploaded
-        # ONCE and prepared once per plan (= per distinct variant shape: the 1/sigma map depends on the template size).
-        q_side = {}
-        for qshape, q_idx in q_groups.items():
-            q_batch = self.dev.stack_to_device([q_items[i] for i in q_idx])
-            by_shape: dict[tuple, list] = {}  # variants of one shape share a plan and the prepared gallery
-            for number, v in enumerate(builder.variants(q_batch, rotations, scales)):
-                vs = tuple(self.dev.shape(v)[2:])
-                by_shape.setdefault(vs, []).append((number, self.dev.astype_storage(v, self.storage)))
+        for b in self._blocks(q_items, g_items, rotations, scales):
+            q_idx, idx = b.q_idx, b.g_idx
+            self.last_chunk_items = b.chunk_items  # (read by the tests)
+            sub = self.dev.zeros((len(q_idx), len(idx)), np.float32)
+            fused = located and all(b.plans[vs].has_peaks for _, vs, _ in b.variants)
+            sub_yx = sub_tag = None
+            if fused:
+                sub_yx = self.dev.to_device(np.full((len(q_idx), len(idx)), -1, dtype=np.int32))
+                sub_tag = self.dev.to_device(np.full((len(q_idx), len(idx)), -1, dtype=np.int32))
+            elif located:
+                second_pass.append((q_idx, idx))
+            for number, vs, v in b.variants:
+                plan = b.plans[vs]
                 if located:
-                    t_hw[q_idx, number] = (vs[0] - 2 * self.crop, vs[1] - 2 * self.crop)
-            q_side[qshape] = by_shape
-        for gshape, g_idx in g_groups.items():
-            plans = {}
-            for qshape, by_shape in q_side.items():
-                if qshape[0] != gshape[0]:
-                    raise ValueError(f"channel mismatch: query {qshape}, gallery {gshape}")
-                for vs in by_shape:
-                    plans[vs] = self.plan(qshape[0], vs, gshape[1:], dtype=self.storage)
-            # every plan's prepared form of a chunk stays alive while the query groups are walked: they share the budget
-            chunk = min(self.gallery_chunk_items(p, len(g_idx), share=len(plans)) for p in plans.values())
-            self.last_chunk_items = chunk  # (read by the tests)
-            for start in range(0, len(g_idx), chunk):
-                idx = g_idx[start:start + chunk]
-                g_batch = self.dev.astype_storage(self.dev.stack_to_device([g_items[i] for i in idx]), self.storage)
-                prepared = {}  # plan -> prepared gallery chunk
-                for qshape, q_idx in q_groups.items():
-                    sub = self.dev.zeros((len(q_idx), len(idx)), np.float32)
-                    fused = located and all(plans[vs].has_peaks for vs in q_side[qshape])
-                    sub_yx = sub_tag = None
-                    if fused:
-                        sub_yx = self.dev.to_device(np.full((len(q_idx), len(idx)), -1, dtype=np.int32))
-                        sub_tag = self.dev.to_device(np.full((len(q_idx), len(idx)), -1, dtype=np.int32))
-                    elif located:
-                        second_pass.append((q_idx, idx))
-                    for vs, vlist in q_side[qshape].items():
-                        plan = plans[vs]
-                        if vs not in prepared:
-                            prepared[vs] = self.prepare_gallery(plan, g_batch)
-                        for number, v in vlist:
-                            pq = self.prepare_queries(plan, v)
-                            self.score_prepared(plan, pq, len(q_idx), prepared[vs], len(idx), sub, len(idx), 0,
-                                                accumulate_max=True, peaks=sub_yx, tags=sub_tag, tag=number)
-                    sub_h = self.dev.to_host(sub)
-                    block = out[np.ix_(q_idx, idx)]
-                    out[np.ix_(q_idx, idx)] = np.maximum(block, sub_h)
-                    if fused:
-                        packed = self.dev.to_host(sub_yx).astype(np.int32, copy=False)
-                        variant[np.ix_(q_idx, idx)] = self.dev.to_host(sub_tag)
-                        yx[np.ix_(q_idx, idx)] = np.where((packed < 0)[..., None], -1,
-                                                         np.stack([packed >> 16, packed & 0xFFFF], axis=-1))
+                    t_hw[q_idx, number] = (vs[0] - 2 * self.crop, vs[1] - 2 * self.crop)  # (the same in every chunk)
+                pg = b.prepared(vs)
+                self.score_prepared(plan, self.prepare_queries(plan, v), len(q_idx), pg, len(idx), sub, len(idx), 0,
+                                    accumulate_max=True, peaks=sub_yx, tags=sub_tag, tag=number)
+            out[np.ix_(q_idx, idx)] = np.maximum(out[np.ix_(q_idx, idx)], self.dev.to_host(sub))
+            if fused:
+                packed = self.dev.to_host(sub_yx).astype(np.int32, copy=False)
+                variant[np.ix_(q_idx, idx)] = self.dev.to_host(sub_tag)
+                yx[np.ix_(q_idx, idx)] = np.where((packed < 0)[..., None], -1,
+                                                 np.stack([packed >> 16, packed & 0xFFFF], axis=-1))
         if located and second_pass and fill_unfused:
             pairs = np.array([(q, g) for q_idx, idx in second_pass for q in q_idx for g in idx], dtype=np.int64)
             _, p_variant, p_yx, _ = self._locate(q_items, g_items, pairs, rotations, scales)
@@ -545,13 +519,25 @@ def _require_contiguous(buf, name: str) -> None:
         raise ValueError(f"{name} must be contiguous")
 
 
-def _group_by_shape(items) -> dict[tuple, list[int]]:
+def _group_by_shape(items, used=None) -> dict[tuple, list[int]]:
+    """Shape -> indices of the items of that shape, of all items or of those ``used`` names."""
     groups: dict[tuple, list[int]] = {}
-    for i, a in enumerate(items):
-        if a.ndim != 3:
+    for i in range(len(items)) if used is None else used:
+        if items[i].ndim != 3:
             raise ValueError("feature maps must be [C, h, w] (customtypes.py:11-14)")
-        groups.setdefault(tuple(a.shape), []).append(i)
+        groups.setdefault(tuple(items[i].shape), []).append(i)
     return groups
+
+
+class _Block(NamedTuple):
+    """One (gallery chunk, query shape class) of ``NccScorer._blocks``."""
+
+    q_idx: list        # the class's query indices, in the order of its variant batches
+    variants: list     # [(variant number, variant (h, w), device batch [len(q_idx), C, h, w] in storage type), ...], ascending
+    g_idx: list        # the chunk's gallery indices
+    plans: dict        # variant (h, w) -> plan against the gallery class
+    chunk_items: int   # the chunk size the budget gave this gallery class
+    prepared: Any      # prepared(variant (h, w)) -> the chunk's prepared form for that plan
 
 
 # ---------------------------------------------------------------------------------------------
@@ -644,8 +630,6 @@ def retrieve(
     ``locate`` - for each of them the best query variant, the peak of its NCC map and the offset
     ``(y - th//2, x - tw//2)`` at which the cropped ``th x tw`` variant template lies on the cropped gallery map.
     ``config["comparison"]`` supplies rotations and scales as for ``compare_maps``."""
-    comp = config["comparison"]
-    rotations, scales = comp.get("rotations"), comp.get("scales")
     return retrieve_with_scores(shoemark_maps, shoeprint_maps, config, k, locate=locate, scorer=scorer)[1]
 
 
@@ -688,44 +672,41 @@ def _shortlist(scorer: NccScorer, shoemark_maps, shoeprint_maps, scores: np.ndar
     if len(qs) == 0:
         return out
     gs = out.index[qs, ps]
+
+    def put(qs, ps, variant, yx, t_hw):
+        out.variant[qs, ps], out.peak_yx[qs, ps], out.offset[qs, ps] = variant, yx, yx - t_hw // 2
+
     if located is not None:
         all_variant, all_yx, all_t_hw = located
-        variant, yx = all_variant[qs, gs], all_yx[qs, gs]
-        out.variant[qs, ps] = variant
-        out.peak_yx[qs, ps] = yx
-        out.offset[qs, ps] = yx - all_t_hw[qs, np.maximum(variant, 0)] // 2
+        variant = all_variant[qs, gs]
+        put(qs, ps, variant, all_yx[qs, gs], all_t_hw[qs, np.maximum(variant, 0)])
         rest = variant < 0
         qs, ps, gs = qs[rest], ps[rest], gs[rest]
         if len(qs) == 0:
             return out
-    _, variant, yx, t_hw = scorer._locate(shoemark_maps, shoeprint_maps, np.stack([qs, gs], axis=1), rotations, scales)
-    out.variant[qs, ps] = variant
-    out.peak_yx[qs, ps] = yx
-    out.offset[qs, ps] = yx - t_hw // 2
+    put(qs, ps, *scorer._locate(shoemark_maps, shoeprint_maps, np.stack([qs, gs], axis=1), rotations, scales)[1:])
     return out
+
+def _pair_maps(scorer: NccScorer | None, template: np.ndarray, image: np.ndarray, crop: int | None) -> np.ndarray:
+    """Host float32 [C, ih, iw] NCC maps of one [C, h, w] template over one [C, h', w'] image."""
+    scorer = scorer or default_scorer()
+    t = np.ascontiguousarray(template, dtype=np.float32)
+    i = np.ascontiguousarray(image, dtype=np.float32)
+    plan = scorer.plan(t.shape[0], t.shape[1:], i.shape[1:], crop=crop)
+    pq = scorer.prepare_queries(plan, scorer.dev.to_device(t[None]))
+    pg = scorer.prepare_gallery(plan, scorer.dev.to_device(i[None]))
+    return scorer.dev.to_host(scorer.ncc_maps_device(plan, pq, pg))
 
 
 def get_similarity(shoemark: np.ndarray, shoeprint: np.ndarray, *, scorer: NccScorer | None = None) -> np.floating[Any]:
     """max over positions of the channel-summed NCC maps, divided by the channel count
     (similarity.py:75-108); both stacks are cropped by 2 pixels per edge first."""
-    scorer = scorer or default_scorer()
-    mark = np.ascontiguousarray(shoemark, dtype=np.float32)
-    prnt = np.ascontiguousarray(shoeprint, dtype=np.float32)
-    plan = scorer.plan(mark.shape[0], mark.shape[1:], prnt.shape[1:])
-    pq = scorer.prepare_queries(plan, scorer.dev.to_device(mark[None]))
-    pg = scorer.prepare_gallery(plan, scorer.dev.to_device(prnt[None]))
-    maps = scorer.dev.to_host(scorer.ncc_maps_device(plan, pq, pg)).astype(np.float64)
-    return np.max(maps.sum(axis=0)) / mark.shape[0]
+    maps = _pair_maps(scorer, shoemark, shoeprint, None).astype(np.float64)
+    return np.max(maps.sum(axis=0)) / maps.shape[0]
 
 
 def normxcorr(template: np.ndarray, image: np.ndarray, mode: str = "same", *, scorer: NccScorer | None = None) -> np.ndarray:
     """Normalised cross-correlation map of ``template`` over ``image`` (similarity.py:26-72)."""
     if mode != "same":
         raise NotImplementedError("only mode='same' is on the hot path (similarity.py:104)")
-    scorer = scorer or default_scorer()
-    t = np.ascontiguousarray(template, dtype=np.float32)
-    i = np.ascontiguousarray(image, dtype=np.float32)
-    plan = scorer.plan(1, t.shape, i.shape, crop=0)
-    pq = scorer.prepare_queries(plan, scorer.dev.to_device(t[None, None]))
-    pg = scorer.prepare_gallery(plan, scorer.dev.to_device(i[None, None]))
-    return scorer.dev.to_host(scorer.ncc_maps_device(plan, pq, pg))[0]
+    return _pair_maps(scorer, np.asarray(template)[None], np.asarray(image)[None], 0)[0]

@@ -19,6 +19,7 @@ from oracle import ncc_oracle as oracle
 from parity_cases import GOLDEN, TIGHT
 from shortlist_cases import POSITION_LEAD
 from shoeprint_image_retrieval_amd import _lib, similarity, synth
+from shoeprint_image_retrieval_amd.variants import VariantBuilder, variant_labels
 
 GUARD = 8
 POISON_F, POISON_I = 777.0, -777
@@ -352,6 +353,119 @@ def check_has_peaks(make_scorer):
         assert sc.lib.spr_ncc_plan_has_peaks(plan.handle) == want and plan.has_peaks == bool(want)
         sc.close()
     assert sc.lib.spr_ncc_plan_has_peaks(None) == 0
+
+
+# (method, storage, calls counted); the matrix-core scorer has no peak form: the unfused path (its plain score_matrix is the
+# other scorers' walk, launch for launch, and the emulation of its pair kernel is slow)
+CALL_COUNT_SCORERS = [("fft", "float32", ("score_matrix", "score_matrix_located", "locate")),
+                      ("direct", "float32", ("score_matrix", "score_matrix_located", "locate")),
+                      ("mfma", "bfloat16", ("score_matrix_located", "locate"))]
+COUNTED = ("spr_ncc_prepare_gallery", "spr_ncc_prepare_queries", "spr_ncc_score", "spr_ncc_score_peaks", "spr_ncc_maps")
+
+
+def count_calls(monkeypatch, lib):
+    """A dict that counts, from now on, the VariantBuilder.variants calls ("expansions") and those of the COUNTED entry points."""
+    n = dict.fromkeys(COUNTED + ("expansions",), 0)
+
+    def counting(name, real):
+        def call(*a, **kw):
+            n[name] += 1
+            return real(*a, **kw)
+        return call
+
+    for name in COUNTED:
+        monkeypatch.setattr(lib, name, counting(name, getattr(lib, name)))
+    monkeypatch.setattr(VariantBuilder, "variants", counting("expansions", VariantBuilder.variants))
+    return n
+
+
+def check_call_counts(make_scorer, monkeypatch, counted=("score_matrix", "score_matrix_located", "locate")):
+    """How often score_matrix, score_matrix_located and locate expand, prepare and launch on the ragged set under one
+    rotation and one scale, against counts derived here from the shapes, the pair list and the budget alone:
+
+    * every query shape class of the call is expanded once;
+    * a gallery chunk is prepared once per distinct variant shape of the query classes that meet it, whatever the number of
+      classes and variants of that shape;
+    * queries are prepared, and the pair kernels launched, once per (chunk, query class, variant);
+    * the chunk size of a gallery class is min over its plans of budget // (number of plans) // bytes per item, at least 1;
+    * locate visits only the classes and chunks of the items its pairs name, with one spr_ncc_maps call per pair and variant;
+    * a scorer without a peak form adds to score_matrix_located a locate over every pair, a scorer with one adds nothing.
+
+    The variant list is [original, scaled, rotated-then-scaled]: the last two share a shape, so each query class brings two
+    variant shapes for three variants.  (Two shape classes of the ragged set - 18 x 12 and 16 x 14 - cannot share a variant
+    shape under one scale s: that needs int(18 s) == int(16 s) and int(12 s) == int(14 s), or a scaled class equal to the other
+    as it is, 16 s >= 18 with 14 s < 13 or 18 s < 17 with 12 s >= 14; none has a solution with maps larger than the crop.)
+    The budget holds one item of each of a gallery class's four prepared forms and splits the two-item class into two chunks
+    for the scoring walk; locate's pairs leave the 16 x 14 query and the 16 x 14 and 17 x 15 gallery items untouched."""
+    rq, rg = ragged_set()
+    rot, scale = [180], [0.9]
+    n_variants = 3
+    pairs = [(0, 0), (2, 3), (0, 1), (2, 0)]
+    assert len(variant_labels(rot, scale)) == n_variants
+
+    def shapes_of(a):  # the variant shapes of an item, in variant order
+        h, w = a.shape[1:]
+        scaled = (int(h * scale[0]), int(w * scale[0]))
+        return [(h, w), scaled, scaled]
+
+    def classes(items, used):
+        groups = {}
+        for i in used:
+            groups.setdefault(items[i].shape[1:], []).append(i)
+        return groups
+
+    every = [(qi, gi) for qi in range(len(rq)) for gi in range(len(rg))]
+    keys = ("expansions", "spr_ncc_prepare_gallery", "spr_ncc_prepare_queries", "launches", "spr_ncc_maps")
+
+    def expected(sc, pair_list=None):
+        """Counts of one walk: the scoring walk over everything (pair_list None) or locate over pair_list."""
+        todo = every if pair_list is None else pair_list
+        q_classes = classes(rq, sorted({qi for qi, _ in todo}))
+        g_classes = classes(rg, sorted({gi for _, gi in todo}))
+        want = dict.fromkeys(keys, 0)
+        want["expansions"] = len(q_classes)
+        for g_hw, g_idx in g_classes.items():
+            plan_shapes = sorted({vs for q_idx in q_classes.values() for vs in shapes_of(rq[q_idx[0]])})
+            per_item = [sc.plan(6, vs, g_hw, dtype=sc.storage).gallery_item_bytes for vs in plan_shapes]
+            chunk = max(1, min(len(g_idx), min(sc.max_prepared_bytes // len(plan_shapes) // b for b in per_item)))
+            for start in range(0, len(g_idx), chunk):
+                part = g_idx[start:start + chunk]
+                met = [q_idx for q_idx in q_classes.values() if any(qi in q_idx and gi in part for qi, gi in todo)]
+                want["spr_ncc_prepare_gallery"] += len({vs for q_idx in met for vs in shapes_of(rq[q_idx[0]])})
+                want["spr_ncc_prepare_queries"] += len(met) * n_variants
+        if pair_list is None:
+            want["launches"] = want["spr_ncc_prepare_queries"]
+        else:
+            want["spr_ncc_maps"] = len(pair_list) * n_variants
+        return want
+
+    sc = make_scorer()
+    two_item_class = [sc.plan(6, vs, (18, 12), dtype=sc.storage) for q in rq[:2] for vs in set(shapes_of(q))]
+    assert len({p.q_hw for p in two_item_class}) == 4
+    budget = 4 * max(p.gallery_item_bytes for p in two_item_class) * 1 + 17  # room for one item of every form, not for two
+    sc.close()
+    sc = make_scorer(max_prepared_bytes=budget)
+    fused = all(sc.plan(6, vs, g.shape[1:], dtype=sc.storage).has_peaks for q in rq for vs in shapes_of(q) for g in rg)
+    n = count_calls(monkeypatch, sc.lib)
+    for name, call, pair_list in (("score_matrix", lambda: sc.score_matrix(rq, rg, rotations=rot, scales=scale), None),
+                                  ("score_matrix_located", lambda: sc.score_matrix_located(rq, rg, rotations=rot, scales=scale), None),
+                                  ("locate", lambda: sc.locate(rq, rg, pairs, rotations=rot, scales=scale), pairs)):
+        if name not in counted:
+            continue
+        before = dict(n)
+        call()
+        got = {k: n[k] - before[k] for k in n}
+        got["launches"] = got.pop("spr_ncc_score") + got.pop("spr_ncc_score_peaks")
+        want = expected(sc, pair_list)
+        if pair_list is None:
+            # the same in closed form: Qc = 2 query classes, V = 3 variants, S_g = 4 variant shapes, sum of K_g = 5 chunks
+            # (four gallery classes, the two-item one in two chunks)
+            assert want["spr_ncc_prepare_gallery"] == 5 * 4 and want["launches"] == 5 * 2 * n_variants
+        if name == "score_matrix_located" and not fused:  # the second pass: a locate over every pair
+            want = {k: want[k] + v for k, v in expected(sc, every).items()}
+        print(f"[call counts] {name}, budget {budget}: {got}")
+        assert got == want, (name, got, want)
+    sc.close()
 
 
 # ------------------------------------------------------------------------------------------------ 6. edges

@@ -84,6 +84,11 @@ def test_emu_peaks_mfma_keeps_the_second_pass(monkeypatch):
     pc.check_mfma_keeps_the_second_pass(emu_scorer("mfma", storage="bfloat16"), monkeypatch)
 
 
+@pytest.mark.parametrize("method,storage,counted", pc.CALL_COUNT_SCORERS, ids=[c[0] for c in pc.CALL_COUNT_SCORERS])
+def test_emu_peaks_call_counts(method, storage, counted, monkeypatch):
+    pc.check_call_counts(lambda **kw: emu_scorer(method, storage=storage, **kw), monkeypatch, counted)
+
+
 def test_emu_peaks_plan_has_peaks():
     pc.check_has_peaks(_scorer)
 

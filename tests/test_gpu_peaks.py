@@ -91,6 +91,11 @@ def test_peaks_mfma_keeps_the_second_pass(lib, monkeypatch):
     pc.check_mfma_keeps_the_second_pass(_make(lib, "mfma", storage="bfloat16"), monkeypatch)
 
 
+@pytest.mark.parametrize("method,storage,counted", pc.CALL_COUNT_SCORERS, ids=[c[0] for c in pc.CALL_COUNT_SCORERS])
+def test_peaks_call_counts(lib, method, storage, counted, monkeypatch):
+    pc.check_call_counts(lambda **kw: _make(lib, method, storage=storage, **kw), monkeypatch, counted)
+
+
 def test_peaks_plan_has_peaks(scorer):
     pc.check_has_peaks(scorer)
 
