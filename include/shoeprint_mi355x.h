@@ -229,6 +229,42 @@ int spr_resample_axis(const float* in, float* out, int64_t n_maps, int32_t h, in
                       int32_t out_size, const int32_t* bounds, const double* coeffs, int32_t ksize,
                       spr_stream_t stream);
 
+/* ------------------------------------------------------------------ image crop + resize (8-bit LANCZOS)
+ * dataloader.py:217-237 loads every image as image.crop(box).resize((int(w*scale), int(h*scale)), LANCZOS).  This entry point
+ * restates the 8-bit path of Pillow's separable resampler (Resample.c) bit for bit on a ragged batch of decoded images of one
+ * mode: channels = 1 (mode "L", [h, w]) or 3 (mode "RGB", [h, w, 3] interleaved).  Horizontal pass first, its result clamped
+ * to 8 bits in the workspace, then the vertical pass; a pass whose size does not change is skipped, an item neither of whose
+ * sizes changes is copied.  The crop box is only addressing: no cropped copy is made.
+ *
+ * A table of one axis for one (source size, output size) pair is int32: [out][2] (first source index, tap count) followed by
+ * [out][ksize] coefficients in 22-bit fixed point, each in [-2^23, 2^23) (image_resize.py: lanczos_tables).  Per output sample
+ * acc = (1 << 21) + sum(pixel * k) in wrapping 32-bit arithmetic, result = clamp(acc >> 22, 0, 255) (arithmetic shift).
+ * The source size of the horizontal table is box_w, of the vertical table box_h; items may share tables.
+ *
+ * spr_image_resize_layout (host only, no device work): checks every item of the HOST array, fills in its `filled by the
+ * layout` members, and returns the workspace size (may be 0) and the two launch sizes that spr_image_resize_u8 takes.  An item
+ * with an output size below 1, a box outside the image, or a table on a pass that keeps its size (or none on one that does
+ * not) gives SPR_ERR_ARG.  n == 0 is valid.
+ * spr_image_resize_u8: in / out / tables / workspace and the array of n laid-out items are DEVICE memory, `blocks` the two
+ * host integers of the layout; offsets of an item are bytes from `in` and `out`, its table offsets count int32 from `tables`.
+ * Two launches whatever n is.  in, out and the workspace may not overlap; the workspace pointer must not be null even where
+ * its size is 0.  n == 0 launches nothing. */
+typedef struct spr_image_resize_item {
+  int64_t in_off;    /* bytes from `in` to the first pixel of the decoded image */
+  int64_t out_off;   /* bytes from `out` to the result, dense [out_h, out_w, channels] */
+  int64_t tmp_off;   /* filled by the layout: the item's horizontal result in the workspace */
+  int32_t in_h, in_w, in_stride;          /* decoded image; row stride in bytes */
+  int32_t box_x, box_y, box_w, box_h;     /* crop box inside it */
+  int32_t out_w, out_h;
+  int32_t htab, vtab;                     /* offset of the axis' table, -1 where box_w == out_w / box_h == out_h */
+  int32_t hk, vk;                         /* ksize of each table */
+  int32_t tmp_stride, hblock0, vblock0;   /* filled by the layout */
+} spr_image_resize_item;
+int spr_image_resize_layout(spr_image_resize_item* items, int64_t n, int32_t channels, size_t* workspace_bytes,
+                            int32_t* blocks);
+int spr_image_resize_u8(const uint8_t* in, uint8_t* out, const spr_image_resize_item* items, int64_t n, int32_t channels,
+                        const int32_t* tables, const int32_t* blocks, void* workspace, spr_stream_t stream);
+
 /* ------------------------------------------------------------------ feature extractor (VGG16)
  *
  * network.py:125-134, 185-186: torchvision vgg16().features truncated to its first `block` children

@@ -33,6 +33,17 @@ class NccShape(C.Structure):
     ]
 
 
+class ImageResizeItem(C.Structure):  # spr_image_resize_item
+    _fields_ = [
+        ("in_off", C.c_int64), ("out_off", C.c_int64), ("tmp_off", C.c_int64),
+        ("in_h", C.c_int32), ("in_w", C.c_int32), ("in_stride", C.c_int32),
+        ("box_x", C.c_int32), ("box_y", C.c_int32), ("box_w", C.c_int32), ("box_h", C.c_int32),
+        ("out_w", C.c_int32), ("out_h", C.c_int32),
+        ("htab", C.c_int32), ("vtab", C.c_int32), ("hk", C.c_int32), ("vk", C.c_int32),
+        ("tmp_stride", C.c_int32), ("hblock0", C.c_int32), ("vblock0", C.c_int32),
+    ]
+
+
 class SprError(RuntimeError):
     """A C-ABI call returned a non-zero status."""
 
@@ -65,6 +76,8 @@ SIGNATURES = {
     "spr_maps_peak": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _VP, _VP, _VP]),
     "spr_rotate_nearest": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, C.POINTER(_I64), _VP]),
     "spr_resample_axis": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
+    "spr_image_resize_layout": (C.c_int, [_VP, _I64, _I32, C.POINTER(_SZ), C.POINTER(_I32)]),
+    "spr_image_resize_u8": (C.c_int, [_VP, _VP, _VP, _I64, _I32, _VP, C.POINTER(_I32), _VP, _VP]),
     "spr_clahe_workspace_bytes": (_SZ, [_I64, _I32, _I32]),
     "spr_clahe_u8": (C.c_int, [_VP, _VP, _I64, _I32, _I32, C.c_float, _I32, _I32, _VP, _VP]),
     "spr_color_tables_bytes": (_SZ, []),

@@ -3,7 +3,7 @@
 The reference reads the file with the ``toml`` package; ``tomli`` (same TOML 1.0 grammar) is what
 this image ships.  As in the reference, ``rotations = ""`` / ``scales = ""`` mean "none"
 (config.py:60-63).  Reference files stay valid: keys under ``[mi355x]`` are build-only extras
-(``dtype``, ``ncc_method``, ``max_prepared_gib``, ``weights``, ``shortlist`` ...) and all have defaults.
+(``dtype``, ``ncc_method``, ``max_prepared_gib``, ``weights``, ``shortlist``, ``device_resize`` ...) and all have defaults.
 """
 
 from __future__ import annotations
@@ -49,6 +49,8 @@ class Mi355xConfig(TypedDict, total=False):
     gallery_cache: str  # directory for persisted gallery features (feature_cache.py); "" = off
     extractor_dtype: str  # "float32" (the reference's arithmetic) | "bfloat16" | "float16": compute type of the extractor
     shortlist: int  # 1 .. 256: run_mi355x.py also prints, per query, that many best gallery prints with variant and offset
+    device_resize: bool  # the loader's crop + LANCZOS resize of "L" / "RGB" images runs on the device (image_resize.py)
+    max_decoded_gib: float  # with device_resize: decoded gallery images kept in device memory between clusters, at most
 
 
 class Config(TypedDict, total=False):
@@ -60,7 +62,7 @@ class Config(TypedDict, total=False):
 
 MI355X_DEFAULTS: dict[str, Any] = {"dtype": "float32", "ncc_method": "auto", "max_prepared_gib": 0.0, "weights": "",
                                    "gallery_cache": "", "extractor_dtype": "float32", "f32_matrix_cores": False,
-                                   "shortlist": 0}
+                                   "shortlist": 0, "device_resize": False, "max_decoded_gib": 8.0}
 
 
 def normalise(raw: dict) -> Config:
@@ -73,6 +75,11 @@ def normalise(raw: dict) -> Config:
     shortlist = extra["shortlist"]
     if isinstance(shortlist, bool) or not isinstance(shortlist, int) or not 0 <= shortlist <= 256:
         raise ValueError(f"[mi355x].shortlist = {shortlist!r}: expected an integer in [0, 256] (0 = off)")
+    if not isinstance(extra["device_resize"], bool):
+        raise ValueError(f"[mi355x].device_resize = {extra['device_resize']!r}: expected true or false")
+    budget = extra["max_decoded_gib"]
+    if isinstance(budget, bool) or not isinstance(budget, (int, float)) or budget < 0:
+        raise ValueError(f"[mi355x].max_decoded_gib = {budget!r}: expected a number of GiB >= 0 (0 = keep nothing)")
     raw["mi355x"] = extra
     return raw  # type: ignore[return-value]
 

@@ -3,7 +3,8 @@
 Host-side mirror of the reference's ``dataloader.py`` (``Dataloader(config)`` is an iterator over size
 clusters of the query images; each step yields ``(query images, ALL gallery images at the cluster's scale,
 gallery index of every query's true match, network block)`` — dataloader.py:26-113).  This is CPU I/O that
-runs once per image; it uses Pillow like the reference does.
+runs once per image; it uses Pillow like the reference does.  The crop + LANCZOS resize, which runs
+once per image *per cluster*, can run on the device instead (``[mi355x] device_resize``, see ``Dataloader``).
 
 Behaviour kept from the reference because it decides the scale and block (and therefore the ranks):
   * "Algorithm 1" scale / block search incl. its asymmetric skip-block loops       (dataloader.py:366-419)
@@ -33,11 +34,30 @@ import numpy as np
 from PIL import Image
 
 
-class Dataloader:
-    """Initialise, pre-process and provide access to datasets (reference dataloader.py:26-113)."""
+_CHUNK_IMAGES = 64  # decoded images per device resize call ([mi355x] device_resize)
 
-    def __init__(self, config: dict) -> None:
+
+class Dataloader:
+    """Initialise, pre-process and provide access to datasets (reference dataloader.py:26-113).
+
+    ``[mi355x] device_resize = true``: files are decoded by the thread pool as before, and the crop + LANCZOS resize of
+    mode-"L" and mode-"RGB" images runs on the device (image_resize.DeviceResizer, byte-identical to Pillow), one call per
+    chunk of images; every other mode goes through Pillow per image.  The decoded gallery stays in device memory, up to
+    ``[mi355x] max_decoded_gib``, so later clusters - which resize the whole gallery again at their own scale - neither read
+    nor decode its files again.  ``resizer``: the DeviceResizer to use (default: one on the current GPU)."""
+
+    def __init__(self, config: dict, resizer=None) -> None:
         self.config = config
+        extra = config.get("mi355x", {})
+        self._device_resize = bool(extra.get("device_resize", False))
+        self._resizer = resizer
+        if self._device_resize and resizer is None:
+            from .image_resize import DeviceResizer
+
+            self._resizer = DeviceResizer()  # raises without a GPU or the library: no fallback
+        self._decoded_budget = int(float(extra.get("max_decoded_gib", 8.0)) * (1 << 30))
+        self._decoded_bytes = 0
+        self._kept: dict[tuple[str, int], Any] = {}  # (directory, chunk) -> decoded chunk resident on the device
         self.dataset_dir = Path(config["dataset"]["dir"])
         self.shoeprint_dir = self.dataset_dir / "Gallery"
         self.shoemark_dir = self.dataset_dir / "Query"
@@ -58,7 +78,7 @@ class Dataloader:
             raise StopIteration
         scale = self.scales[self._current_cluster]
         shoemark_images, shoemark_ids = self._load_images(self.clusters[self._current_cluster], self.shoemark_dir, scale)
-        shoeprint_images, shoeprint_ids = self._load_images(self.shoeprint_files, self.shoeprint_dir, scale)
+        shoeprint_images, shoeprint_ids = self._load_images(self.shoeprint_files, self.shoeprint_dir, scale, keep=True)
         if self.config["dataset"]["type"] != "FID-300":
             # ValueError if a query's id has no gallery item, as list.index does in the reference (:99)
             matching_pairs = [shoeprint_ids.index(i) for i in shoemark_ids]
@@ -73,14 +93,43 @@ class Dataloader:
         return shoemark_images, shoeprint_images, matching_pairs, block
 
     # ------------------------------------------------------------------ loading
-    def _load_images(self, image_files: list[str], image_directory: Path, scale: float):
+    def _load_images(self, image_files: list[str], image_directory: Path, scale: float, keep: bool = False):
         files = sorted(image_files)
         crop = self.config["dataset"]["crop"]
         kind = self.config["dataset"]["type"]
         workers = max(1, min(int(self.config["dataset"].get("n_processes", 1)), len(files) or 1))
         with ThreadPoolExecutor(workers) as pool:
+            if self._device_resize:
+                return self._load_images_device(pool, files, image_directory, scale, crop, kind, keep)
             loaded = list(pool.map(lambda f: _load_one(image_directory / f, f, scale, crop, kind), files))
         return [im for im, _ in loaded], [i for _, i in loaded]
+
+    def _load_images_device(self, pool, files, directory: Path, scale: float, crop, kind: str, keep: bool):
+        """``keep``: the directory is loaded again by every cluster (the gallery): its decoded chunks stay on the device
+        while they fit the budget."""
+        from .image_resize import crop_box
+
+        idents = [_parse_id(f, kind) for f in files]
+        images: list[Any] = [None] * len(files)
+        for c, start in enumerate(range(0, len(files), _CHUNK_IMAGES)):
+            names = files[start: start + _CHUNK_IMAGES]
+            key = (str(directory), c)
+            chunk = self._kept.get(key) if keep else None
+            if chunk is None:
+                decoded = list(pool.map(lambda f: _decode_image(directory / f), names))
+                chunk = _DecodedChunk(self._resizer, decoded)
+                if keep and self._decoded_bytes + chunk.nbytes <= self._decoded_budget:
+                    self._kept[key] = chunk
+                    self._decoded_bytes += chunk.nbytes
+            for where, resident in chunk.groups:
+                boxes = [crop_box(w, h, crop) for h, w in resident.shapes]
+                sizes = [(int(b[2] * scale), int(b[3] * scale)) for b in boxes]
+                for k, out in zip(where, self._resizer.resize_resident(resident, boxes, sizes)):
+                    images[start + k] = out
+            others = list(pool.map(lambda k: _load_one(directory / names[k], names[k], scale, crop, kind)[0], chunk.others))
+            for k, out in zip(chunk.others, others):
+                images[start + k] = out
+        return images, idents
 
     # ------------------------------------------------------------------ clustering
     def _cluster_images_by_size(self, image_dir: Path, n_clusters: int) -> dict[int, list[str]]:
@@ -171,6 +220,35 @@ def _load_one(path: Path, name: str, scale: float, crop, dataset_type: str) -> t
         image = image.crop((crop_width, crop_height, image.width - crop_width, image.height - crop_height))
         resized = image.resize((int(image.width * scale), int(image.height * scale)), Image.Resampling.LANCZOS)
         array = np.array(resized)
+    return array, _parse_id(name, dataset_type)
+
+
+def _decode_image(path: Path) -> np.ndarray | None:
+    """The decoded pixels of a mode-"L" ([h, w]) or mode-"RGB" ([h, w, 3]) file; None for any other mode, which Pillow
+    resizes by rules of its own (NEAREST for "1" and "P", premultiplied alpha, 16-bit and float arithmetic)."""
+    with Image.open(path) as image:
+        if image.mode not in ("L", "RGB"):
+            return None
+        return np.array(image)
+
+
+class _DecodedChunk:
+    """One chunk of a directory, decoded: the "L" and the "RGB" images each packed into a device buffer (``groups``: positions
+    in the chunk and the resident images), and the positions of the files of other modes."""
+
+    def __init__(self, resizer, decoded: list):
+        self.others = [k for k, a in enumerate(decoded) if a is None]
+        self.groups = []
+        self.nbytes = 0
+        for ndim in (2, 3):
+            where = [k for k, a in enumerate(decoded) if a is not None and a.ndim == ndim]
+            if where:
+                resident = resizer.upload([decoded[k] for k in where])
+                self.groups.append((where, resident))
+                self.nbytes += resident.nbytes
+
+
+def _parse_id(name: str, dataset_type: str) -> int:
     if dataset_type == "Impress":
         ident = int(name.split("_")[0].split(".")[0])
     elif dataset_type == "WVU2019":
@@ -179,4 +257,4 @@ def _load_one(path: Path, name: str, scale: float, crop, dataset_type: str) -> t
         ident = int(name[:-4])
     else:
         raise ValueError(f"unknown dataset type {dataset_type!r} (FID-300, Impress or WVU2019)")
-    return array, ident
+    return ident
