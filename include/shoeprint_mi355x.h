@@ -151,11 +151,20 @@ int spr_ncc_score(spr_ncc_plan* plan, const void* prepared_queries, int64_t n_qu
  *    caller that walks variants in another order than their numbers still ends with the lowest number among equal scores);
  *    otherwise it is left alone.  The caller starts the three matrices at 0 / -1 / -1.  The stored tag is read and compared
  *    only when peak_tag is given.
- *  - Limits and launch slicing as for spr_ncc_score.  spr_ncc_plan_has_peaks: 1 for SPR_NCC_FFT and SPR_NCC_DIRECT plans, 0
- *    for the matrix-core methods (SPR_NCC_MFMA, SPR_NCC_MFMA_F32), whose kernels keep the maximum only: on such a plan
- *    spr_ncc_score_peaks returns SPR_ERR_UNSUPPORTED and launches nothing (locate those pairs with spr_ncc_maps +
- *    spr_maps_peak).  spr_ncc_score and spr_ncc_maps are unchanged. */
+ *  - Limits and launch slicing as for spr_ncc_score.  spr_ncc_plan_has_peaks: 1 for SPR_NCC_FFT and SPR_NCC_DIRECT plans.
+ *    A plan of the matrix-core methods (SPR_NCC_MFMA, SPR_NCC_MFMA_F32) answers 0 unless it was asked for the peak form with
+ *    spr_ncc_plan_enable_peaks (below): by default its kernels keep the maximum only, spr_ncc_score_peaks returns
+ *    SPR_ERR_UNSUPPORTED on it and launches nothing (locate those pairs with spr_ncc_maps + spr_maps_peak).  spr_ncc_score
+ *    and spr_ncc_maps are unchanged, on every plan, asked or not. */
 int spr_ncc_plan_has_peaks(const spr_ncc_plan* plan); /* 1 / 0 */
+/* Ask the plan for the peak form.  SPR_OK on every plan; a no-op on FFT / direct plans.  Afterwards
+ * spr_ncc_plan_has_peaks(plan) == 1 and spr_ncc_score_peaks works on it, by the contract written above
+ * spr_ncc_score_peaks word for word (scores bit for bit those of spr_ncc_score, first maximum of the
+ * kernel's float32 channel sums in row-major order, accumulate / tag rule, limits).  A matrix-core plan takes the arg-max
+ * behind its channel loop in all four forms (bfloat16 exact - after the correction matrix is subtracted -, bfloat16 hi + lo,
+ * float16, float32 hi + lo) and names positions of the cropped search map only, never a spare position of its 28 x 12
+ * frame.  Prepared layouts and sizes do not depend on the call.  SPR_ERR_ARG for a NULL plan. */
+int spr_ncc_plan_enable_peaks(spr_ncc_plan* plan);
 int spr_ncc_score_peaks(spr_ncc_plan* plan, const void* prepared_queries, int64_t n_queries,
                         const void* prepared_gallery, int64_t n_gallery, float* scores, int32_t* peak_yx,
                         int32_t* peak_tag, int64_t ld, int64_t col0, int accumulate_max, int32_t tag,

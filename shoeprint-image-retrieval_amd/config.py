@@ -3,7 +3,7 @@
 The reference reads the file with the ``toml`` package; ``tomli`` (same TOML 1.0 grammar) is what
 this image ships.  As in the reference, ``rotations = ""`` / ``scales = ""`` mean "none"
 (config.py:60-63).  Reference files stay valid: keys under ``[mi355x]`` are build-only extras
-(``dtype``, ``ncc_method``, ``max_prepared_gib``, ``weights``, ``shortlist``, ``device_resize`` ...) and all have defaults.
+(``dtype``, ``ncc_method``, ``max_prepared_gib``, ``weights``, ``shortlist``, ``device_resize``, ``matrix_core_peaks`` ...) and all have defaults.
 """
 
 from __future__ import annotations
@@ -45,6 +45,7 @@ class Mi355xConfig(TypedDict, total=False):
     ncc_method: str
     max_prepared_gib: float
     f32_matrix_cores: bool  # with ncc_method "auto": float32 plans the "mfma_f32" method covers run on the bf16 matrix cores
+    matrix_core_peaks: bool  # plans of the matrix-core methods take the arg-max in the scoring pass (spr_ncc_plan_enable_peaks)
     weights: str
     gallery_cache: str  # directory for persisted gallery features (feature_cache.py); "" = off
     extractor_dtype: str  # "float32" (the reference's arithmetic) | "bfloat16" | "float16": compute type of the extractor
@@ -62,7 +63,8 @@ class Config(TypedDict, total=False):
 
 MI355X_DEFAULTS: dict[str, Any] = {"dtype": "float32", "ncc_method": "auto", "max_prepared_gib": 0.0, "weights": "",
                                    "gallery_cache": "", "extractor_dtype": "float32", "f32_matrix_cores": False,
-                                   "shortlist": 0, "device_resize": False, "max_decoded_gib": 8.0}
+                                   "shortlist": 0, "device_resize": False, "max_decoded_gib": 8.0,
+                                   "matrix_core_peaks": False}
 
 
 def normalise(raw: dict) -> Config:
@@ -77,6 +79,8 @@ def normalise(raw: dict) -> Config:
         raise ValueError(f"[mi355x].shortlist = {shortlist!r}: expected an integer in [0, 256] (0 = off)")
     if not isinstance(extra["device_resize"], bool):
         raise ValueError(f"[mi355x].device_resize = {extra['device_resize']!r}: expected true or false")
+    if not isinstance(extra["matrix_core_peaks"], bool):
+        raise ValueError(f"[mi355x].matrix_core_peaks = {extra['matrix_core_peaks']!r}: expected true or false")
     budget = extra["max_decoded_gib"]
     if isinstance(budget, bool) or not isinstance(budget, (int, float)) or budget < 0:
         raise ValueError(f"[mi355x].max_decoded_gib = {budget!r}: expected a number of GiB >= 0 (0 = keep nothing)")

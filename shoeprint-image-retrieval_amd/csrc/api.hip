@@ -71,6 +71,7 @@ struct spr_ncc_plan {
   spr::NccGeom geom;
   int method;              // resolved: SPR_NCC_FFT, SPR_NCC_DIRECT, SPR_NCC_MFMA or SPR_NCC_MFMA_F32
   spr::PlanScratch scratch{};
+  bool mfma_peaks = false;  // matrix-core plans: spr_ncc_plan_enable_peaks was called (their peak form is opt-in)
   // A plan that owns device scratch its kernels write (mfma_x, team_sync, ws) orders its own calls: every scoring call
   // records `done` behind its launches, and a call that arrives on ANOTHER stream waits for it first - two streams sharing a
   // plan (one scorer, equal-shaped layers on separate streams) then serialise instead of racing on the scratch.
@@ -306,7 +307,14 @@ extern "C" int spr_ncc_score(spr_ncc_plan* plan, const void* pq, int64_t nq, con
 }
 
 extern "C" int spr_ncc_plan_has_peaks(const spr_ncc_plan* plan) {
-  return plan && (plan->method == SPR_NCC_FFT || plan->method == SPR_NCC_DIRECT) ? 1 : 0;
+  if (!plan) return 0;
+  return plan->method == SPR_NCC_FFT || plan->method == SPR_NCC_DIRECT || plan->mfma_peaks ? 1 : 0;
+}
+
+extern "C" int spr_ncc_plan_enable_peaks(spr_ncc_plan* plan) {
+  if (!plan) { set_error("spr_ncc_plan_enable_peaks: null plan"); return SPR_ERR_ARG; }
+  if (plan->method == SPR_NCC_MFMA || plan->method == SPR_NCC_MFMA_F32) plan->mfma_peaks = true;  // (the others have the form as they are)
+  return SPR_OK;
 }
 
 extern "C" int spr_ncc_score_peaks(spr_ncc_plan* plan, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores,
@@ -314,7 +322,8 @@ extern "C" int spr_ncc_score_peaks(spr_ncc_plan* plan, const void* pq, int64_t n
                                    int32_t tag, spr_stream_t stream) {
   if (!plan) { set_error("spr_ncc_score_peaks: null plan"); return SPR_ERR_ARG; }
   if (!spr_ncc_plan_has_peaks(plan)) {  // before anything is launched
-    set_error("spr_ncc_score_peaks: the matrix-core methods keep the maximum only (spr_ncc_plan_has_peaks() == 0)");
+    set_error("spr_ncc_score_peaks: the matrix-core methods keep the maximum only (spr_ncc_plan_has_peaks() == 0) unless the "
+              "plan was asked with spr_ncc_plan_enable_peaks");
     return SPR_ERR_UNSUPPORTED;
   }
   if (nq < 0 || ng < 0 || col0 < 0 || ld < col0 + ng) { set_error("spr_ncc_score_peaks: bad sizes"); return SPR_ERR_ARG; }

@@ -109,6 +109,7 @@ bool prep6_covers(const NccGeom& g);  // gallery of a six-wave plan with corner 
 int launch_prep6(const NccGeom& g, const PlanScratch& s, const PrepCall& c);
 int launch_prep_mfma(const NccGeom& g, const PlanScratch& s, const PrepCall& c);  // bf16 / f16 matrix cores (ncc_mfma.hip), both methods
 int launch_pair_mfma(const NccGeom& g, const PlanScratch& s, const PairCall& c);
+int launch_pair_mfma_peaks(const NccGeom& g, const PlanScratch& s, const PairCall& c);  // c.peak_yx set (ncc_mfma_peaks.hip)
 // Pair kernels run one workgroup per pair in tiles of `pairs_per_tile`; HIP refuses a grid of 2^32 work-items or
 // more, so a launch takes at most this many tiles (SPR_NCC_MAX_TILES lowers it: tests of the slicing).
 int64_t pair_tiles_per_launch(int pairs_per_tile, int threads);

@@ -49,12 +49,15 @@ def _dtype_code(dtype) -> tuple[int, str]:
 class _Plan:
     """Owns one spr_ncc_plan (one (query shape, gallery shape) class)."""
 
-    def __init__(self, lib: _lib.Library, channels: int, q_hw, g_hw, crop: int, dtype: int, method: int):
+    def __init__(self, lib: _lib.Library, channels: int, q_hw, g_hw, crop: int, dtype: int, method: int,
+                 enable_peaks: bool = False):
         self.lib = lib
         shape = NccShape(channels, q_hw[0], q_hw[1], g_hw[0], g_hw[1], crop, dtype, method)
         handle = C.c_void_p()
         lib.check(lib.spr_ncc_plan_create(C.byref(shape), C.byref(handle)))
         self.handle = handle
+        if enable_peaks:  # a matrix-core plan's peak form is opt-in; a no-op on the others
+            lib.check(lib.spr_ncc_plan_enable_peaks(handle))
         self.channels, self.q_hw, self.g_hw, self.crop = channels, tuple(q_hw), tuple(g_hw), crop
         self.method = lib.spr_ncc_plan_method(handle)
         rows, cols = C.c_int32(), C.c_int32()
@@ -62,7 +65,8 @@ class _Plan:
         self.fft_size = (rows.value, cols.value)
         self.query_item_bytes = lib.spr_ncc_query_bytes(handle, 1)
         self.gallery_item_bytes = lib.spr_ncc_gallery_bytes(handle, 1)
-        self.has_peaks = bool(lib.spr_ncc_plan_has_peaks(handle))  # spr_ncc_score_peaks: FFT and direct plans
+        # spr_ncc_score_peaks: FFT and direct plans, and matrix-core plans that were asked (enable_peaks)
+        self.has_peaks = bool(lib.spr_ncc_plan_has_peaks(handle))
 
     def close(self):
         if self.handle:
@@ -109,11 +113,15 @@ class NccScorer:
     f32_matrix_cores: with method "auto", a float32 plan first asks for "mfma_f32" (float32 maps as hi + lo on the bf16
         matrix cores: cropped maps up to 28 x 12, cropped templates up to 30 x 16) and takes what "auto" gives where that
         method does not cover the plan - per plan, so ragged sets and query variants mix methods by shape.
+    matrix_core_peaks: every plan is asked for the peak form (spr_ncc_plan_enable_peaks), so plans of the matrix-core
+        methods ("mfma", "mfma_f32", and what "auto" resolves to them) too give position and best variant out of the
+        scoring pass: ``score_matrix_located`` and ``retrieve`` then make no second pass over their blocks.  Off by
+        default: such plans keep the maximum only, as before the form existed.
     """
 
     def __init__(self, device=None, library: _lib.Library | None = None, method: str = "auto",
                  max_prepared_bytes: int | None = None, crop: int = CROP, storage: str = "float32",
-                 f32_matrix_cores: bool = False):
+                 f32_matrix_cores: bool = False, matrix_core_peaks: bool = False):
         self.lib = library or _lib.load_library()
         if device is None:
             from .device import TorchDevice
@@ -127,6 +135,7 @@ class NccScorer:
             raise ValueError(f"unknown storage type {storage!r}")
         self.storage = storage
         self.f32_matrix_cores = bool(f32_matrix_cores)
+        self.matrix_core_peaks = bool(matrix_core_peaks)
         self._plans: dict[tuple, _Plan] = {}
         self._variants = None
 
@@ -139,12 +148,12 @@ class NccScorer:
         if p is None:
             if self.f32_matrix_cores and self.method == NCC_AUTO and code == _lib.F32:
                 try:
-                    p = _Plan(self.lib, channels, q_hw, g_hw, crop, code, _lib.NCC_MFMA_F32)
+                    p = _Plan(self.lib, channels, q_hw, g_hw, crop, code, _lib.NCC_MFMA_F32, self.matrix_core_peaks)
                 except _lib.SprError as e:
                     if e.code != _lib.SPR_ERR_UNSUPPORTED:
                         raise
             if p is None:
-                p = _Plan(self.lib, channels, q_hw, g_hw, crop, code, self.method)
+                p = _Plan(self.lib, channels, q_hw, g_hw, crop, code, self.method, self.matrix_core_peaks)
             self._plans[key] = p
         return p
 
@@ -178,7 +187,8 @@ class NccScorer:
                        accumulate_max: bool = False, peaks=None, tags=None, tag: int = 0):
         """spr_ncc_score; with ``peaks`` (device int32, laid out like ``scores``) spr_ncc_score_peaks: the same scores and
         beside each the position ``(y << 16) | x`` of its maximum, in ``tags`` (optional, same layout) the ``tag`` of the
-        call that stored it.  Plans of the matrix-core methods have no peak form (``plan.has_peaks``): SprError."""
+        call that stored it.  Plans of the matrix-core methods have no peak form unless the scorer was made with
+        ``matrix_core_peaks`` (``plan.has_peaks``): SprError."""
         if peaks is None:
             self.lib.check(self.lib.spr_ncc_score(plan.handle, self.dev.ptr(pq), nq, self.dev.ptr(pg), ng,
                                                   self.dev.ptr(scores), ld, col0, 1 if accumulate_max else 0,
@@ -414,8 +424,9 @@ class NccScorer:
         ``scores``.  ``yx`` is in cropped search-map coordinates; the lowest variant number wins among equal scores.  A pair
         whose score is 0 (no variant's map rises above 0) has variant -1 and yx (-1, -1).  The arg-max is taken on the
         kernels' float32 channel sums, ``locate`` sums the per-channel maps in float64: the two may name different pixels where
-        the two largest sums lie within rounding of each other.  Plans without a peak form (the matrix-core methods) are
-        scored as ever and their blocks located by the second pass of ``locate``."""
+        the two largest sums lie within rounding of each other.  Plans without a peak form (the matrix-core methods of a
+        scorer made without ``matrix_core_peaks``) are scored as ever and their blocks located by the second pass of
+        ``locate``."""
         return self._score_matrix_located(shoemark_maps, shoeprint_maps, rotations, scales)[:3]
 
     def _score_matrix_located(self, shoemark_maps, shoeprint_maps, rotations, scales, fill_unfused: bool = True):
@@ -559,8 +570,8 @@ _config_scorers: dict[tuple, NccScorer] = {}
 def scorer_from_config(config: dict, *, device=None, library: _lib.Library | None = None) -> NccScorer:
     """The scorer that ``[mi355x]`` of run.toml asks for: ``ncc_method`` ("auto" | "fft" | "fft_pow2" | "direct" | "mfma" |
     "mfma_f32"), ``dtype`` (HBM storage type of the feature maps: "float32" | "float16" | "bfloat16"), ``max_prepared_gib``
-    (HBM budget of one prepared gallery chunk; 0 = automatic) and ``f32_matrix_cores`` (see NccScorer).  Reference files,
-    which have no such table, get the defaults."""
+    (HBM budget of one prepared gallery chunk; 0 = automatic), ``f32_matrix_cores`` and ``matrix_core_peaks`` (see
+    NccScorer).  Reference files, which have no such table, get the defaults."""
     extra = config.get("mi355x") or {}
     method = extra.get("ncc_method", "auto") or "auto"
     storage = extra.get("dtype", "float32") or "float32"
@@ -568,12 +579,14 @@ def scorer_from_config(config: dict, *, device=None, library: _lib.Library | Non
     if method not in _METHODS:
         raise ValueError(f"[mi355x].ncc_method = {method!r}: expected one of {sorted(_METHODS)}")
     f32_mc = bool(extra.get("f32_matrix_cores", False))
-    key = (method, storage, gib, f32_mc, id(device), id(library))
-    if key == ("auto", "float32", 0.0, False, id(None), id(None)):
+    mc_peaks = bool(extra.get("matrix_core_peaks", False))
+    key = (method, storage, gib, f32_mc, mc_peaks, id(device), id(library))
+    if key == ("auto", "float32", 0.0, False, False, id(None), id(None)):
         return default_scorer()
     if key not in _config_scorers:
         _config_scorers[key] = NccScorer(device=device, library=library, method=method, storage=storage,
-                                         f32_matrix_cores=f32_mc, max_prepared_bytes=int(gib * (1 << 30)) if gib > 0 else None)
+                                         f32_matrix_cores=f32_mc, matrix_core_peaks=mc_peaks,
+                                         max_prepared_bytes=int(gib * (1 << 30)) if gib > 0 else None)
     return _config_scorers[key]
 
 
