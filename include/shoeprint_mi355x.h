@@ -221,6 +221,28 @@ int spr_topk_rows(const float* scores, int64_t ld, int64_t n_queries, int64_t n_
 int spr_maps_peak(const float* maps, int64_t n_pairs, int32_t channels, int32_t h, int32_t w, float* out_score,
                   int32_t* out_yx, spr_stream_t stream);
 
+/* ------------------------------------------------------------------ device-resident ragged sets (features.py)
+ * spr_items_gather: item k of dst (k < n) is item index[k] of src, converted to dst_dtype (an spr_dtype).  src: device
+ * float32 [*, item_elems], dense; index: DEVICE int32 [n], may repeat, any order, every value a valid item of src (not
+ * checked: the caller owns it); dst: device [n, item_elems] of dst_dtype, dense.  The conversion rounds to nearest even:
+ * on finite inputs the bits are those of torch's .to(float16 / bfloat16); +-inf pass through, float16 overflow gives inf,
+ * -0 is kept, NaN stays NaN (float32 -> float32 copies the bits; a 16-bit NaN's payload is unspecified).  src is only
+ * read, nothing outside [dst, dst + n * item_elems * size) is written.  item_elems need not be a multiple of 4; every
+ * offset is 64-bit (a shape class may exceed 4 GiB) and the grid strides over the items, so n has no limit of its own.
+ * src must be 4-byte aligned and dst aligned to its element size, sizes >= 0 and dst_dtype known, else SPR_ERR_ARG;
+ * n == 0 or item_elems == 0 is a no-op.  This is the upload + cast of one shape class or gallery chunk in one pass. */
+int spr_items_gather(const float* src, int64_t item_elems, const int32_t* index, int64_t n, void* dst, int32_t dst_dtype,
+                     spr_stream_t stream);
+
+/* spr_block_scatter: dst[rows[i] * ld + cols[j]] <- src[i * src_ld + j] for i < nr, j < nc, on 4-byte elements.
+ * mode 0 copies the bits (int32 position / variant matrices); mode 1 stores the float32 maximum of the two (a score
+ * matrix; the entry is left alone unless src is greater, so scores given to accumulate into survive).  rows / cols: DEVICE
+ * int32 [nr] / [nc].  PRECONDITION: the values of rows are distinct and those of cols are distinct, rows[i] * ld + cols[j]
+ * lies inside dst - the kernel cannot check device-side contents, its callers guarantee them.  dst and src must not
+ * overlap.  nr, nc >= 0, mode 0 | 1, ld >= nc and src_ld >= nc, else SPR_ERR_ARG; nr == 0 or nc == 0 is a no-op. */
+int spr_block_scatter(void* dst, int64_t ld, const void* src, int64_t src_ld, const int32_t* rows, int64_t nr,
+                      const int32_t* cols, int64_t nc, int32_t mode, spr_stream_t stream);
+
 /* ------------------------------------------------------------------ query variants (rotation / scale)
  * similarity.py:230-284 pushes every query feature map through Pillow: Image.rotate(angle) (NEAREST, no
  * expand, zero fill) or Image.resize((int(w*s), int(h*s))) (BICUBIC on mode "F").  These two entry

@@ -7,7 +7,9 @@ Same flow: load the config, iterate the size clusters of the query set, extract 
 of the whole gallery with the truncated network chosen for the cluster, rank every query's true match, print
 the S-scores of that cluster against the whole-data-set totals.  Additionally prints rank-1 and mAP over all
 clusters at the end.  With ``[mi355x] shortlist = K`` it also prints, under every query's rank line, the K best gallery
-prints with score, best query variant and the offset at which the mark lies on the print.
+prints with score, best query variant and the offset at which the mark lies on the print.  With ``[mi355x] device_resident = true``
+features and scores stay in device memory from the extractor to the ranks (features.FeatureSet): per cluster only the rank vector
+and the shortlist come back, the printed output and the ranks are the same.
 """
 
 import os
@@ -16,9 +18,10 @@ import sys
 from shoeprint_image_retrieval_amd.config import load_config
 from shoeprint_image_retrieval_amd import feature_cache
 from shoeprint_image_retrieval_amd.dataloader import Dataloader
+from shoeprint_image_retrieval_amd.features import DeviceImages, FeatureSet
 from shoeprint_image_retrieval_amd.network import Model
 from shoeprint_image_retrieval_amd.parse_results import cmp_all, mean_average_precision, rank1
-from shoeprint_image_retrieval_amd.similarity import compare_maps, retrieve_with_scores, scorer_from_config
+from shoeprint_image_retrieval_amd.similarity import compare_maps, retrieve_resident, retrieve_with_scores, scorer_from_config
 from shoeprint_image_retrieval_amd.variants import variant_labels
 
 
@@ -27,8 +30,12 @@ def ranks_with_shortlist(shoemark_features, shoeprint_features, matching_shoepri
     followed by its k best gallery prints."""
     comp = config["comparison"]
     scorer = scorer_from_config(config)
-    scores, short = retrieve_with_scores(shoemark_features, shoeprint_features, config, k, scorer=scorer)
-    ranks = scorer.ranks(scores, matching_shoeprint_ids)
+    if isinstance(shoemark_features, FeatureSet) and isinstance(shoeprint_features, FeatureSet):
+        scores, short = retrieve_resident(shoemark_features, shoeprint_features, config, k, scorer=scorer)
+        ranks = scorer.ranks_of_device(scores, matching_shoeprint_ids)  # (the matrix stays where it is)
+    else:
+        scores, short = retrieve_with_scores(shoemark_features, shoeprint_features, config, k, scorer=scorer)
+        ranks = scorer.ranks(scores, matching_shoeprint_ids)
     labels = variant_labels(comp.get("rotations"), comp.get("scales"))
     for i, r in enumerate(ranks):
         print(f"Print {i} true match ranked {r}")
@@ -41,6 +48,24 @@ def ranks_with_shortlist(shoemark_features, shoeprint_features, matching_shoepri
     return ranks
 
 
+def feature_bytes(model, *image_sets) -> int:
+    """Bytes of the float32 features ``model`` makes of the images (host lists or DeviceImages), from their shapes alone."""
+    total = 0
+    for images in image_sets:
+        shapes = [(s, len(idx)) for s, idx, _ in images.classes] if isinstance(images, DeviceImages) else [(im.shape, 1) for im in images]
+        sizes = {}
+        for shape, n in shapes:
+            if shape[:2] not in sizes:
+                c, h, w = model.output_shape(shape[0], shape[1])
+                sizes[shape[:2]] = 4 * c * h * w
+            total += n * sizes[shape[:2]]
+    return total
+
+
+def _host_images(images):
+    return images.to_host_list() if isinstance(images, DeviceImages) else images
+
+
 def main(config_file: str = "run.toml") -> list[int]:
     config = load_config(config_file)
     dataloader = Dataloader(config)
@@ -50,7 +75,17 @@ def main(config_file: str = "run.toml") -> list[int]:
     for cluster, (shoemark_images, shoeprint_images, matching_shoeprint_ids, block) in enumerate(dataloader):
         print(f"Cluster has {len(shoemark_images)} items.")
         model = Model(config, block)
-        shoemark_features = model.get_multiple_feature_maps(shoemark_images)
+        resident = bool(config["mi355x"].get("device_resident", False))
+        if resident:
+            need, ceiling = feature_bytes(model, shoemark_images, shoeprint_images), float(config["mi355x"].get("max_feature_gib", 64.0))
+            if need > ceiling * (1 << 30):
+                print(f"cluster {cluster}: {need / (1 << 30):.2f} GiB of features exceed [mi355x].max_feature_gib = {ceiling:g}: "
+                      "this cluster takes the host route", file=sys.stderr)
+                resident = False
+        if not resident:
+            shoemark_images, shoeprint_images = _host_images(shoemark_images), _host_images(shoeprint_images)
+        extract = model.get_multiple_feature_maps_device if resident else model.get_multiple_feature_maps
+        shoemark_features = extract(shoemark_images)
         # gallery features depend only on what is in `key`: keep them across runs when [mi355x].gallery_cache is set
         key = {"files": dataloader.shoeprint_files, "scale": dataloader.scales[cluster], "block": block,
                "crop": list(config["dataset"]["crop"]), "model": dict(config["model"]),
@@ -59,12 +94,14 @@ def main(config_file: str = "run.toml") -> list[int]:
         path = os.path.join(cache_dir, f"gallery_block{block}_cluster{cluster}.f32") if cache_dir else ""
         shoeprint_features = feature_cache.load_features(path, key) if path else None
         if shoeprint_features is None:
-            shoeprint_features = model.get_multiple_feature_maps(shoeprint_images)
+            shoeprint_features = extract(shoeprint_images)
             if path:
-                os.makedirs(cache_dir, exist_ok=True)
-                feature_cache.save_features(path, shoeprint_features, key)
+                os.makedirs(cache_dir, exist_ok=True)  # (a resident gallery comes down once, to be written)
+                feature_cache.save_features(path, shoeprint_features.to_host_list() if resident else shoeprint_features, key)
         else:
             print(f"Gallery features from {path}")
+            if resident:
+                shoeprint_features = FeatureSet.from_host(model.dev, shoeprint_features)
         print("Calculating ranks:")
         shortlist = int(config["mi355x"].get("shortlist", 0) or 0)
         if shortlist > 0:

@@ -75,7 +75,9 @@ SIGNATURES = {
     "spr_scores_fuse": (C.c_int, [_VP, _VP, _I64, C.c_float, C.c_float, _VP]),
     "spr_topk_rows": (C.c_int, [_VP, _I64, _I64, _I64, _VP, _I64, _I32, _VP, _VP, _VP]),
     "spr_maps_peak": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _VP, _VP, _VP]),
-    "spr_rotate_nearest": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, C.POINTER(_I64), _VP]),
+    "spr_items_gather": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _I32, _VP]),
+    "spr_block_scatter": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _I32, _VP]),
+    "spr_rotate_nearest":(C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, C.POINTER(_I64), _VP]),
     "spr_resample_axis": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
     "spr_image_resize_layout": (C.c_int, [_VP, _I64, _I32, C.POINTER(_SZ), C.POINTER(_I32)]),
     "spr_image_resize_u8": (C.c_int, [_VP, _VP, _VP, _I64, _I32, _VP, C.POINTER(_I32), _VP, _VP]),

@@ -3,7 +3,7 @@
 The reference reads the file with the ``toml`` package; ``tomli`` (same TOML 1.0 grammar) is what
 this image ships.  As in the reference, ``rotations = ""`` / ``scales = ""`` mean "none"
 (config.py:60-63).  Reference files stay valid: keys under ``[mi355x]`` are build-only extras
-(``dtype``, ``ncc_method``, ``max_prepared_gib``, ``weights``, ``shortlist``, ``device_resize``, ``matrix_core_peaks`` ...) and all have defaults.
+(``dtype``, ``ncc_method``, ``max_prepared_gib``, ``weights``, ``shortlist``, ``device_resize``, ``matrix_core_peaks``, ``device_resident`` ...) and all have defaults.
 """
 
 from __future__ import annotations
@@ -52,6 +52,8 @@ class Mi355xConfig(TypedDict, total=False):
     shortlist: int  # 1 .. 256: run_mi355x.py also prints, per query, that many best gallery prints with variant and offset
     device_resize: bool  # the loader's crop + LANCZOS resize of "L" / "RGB" images runs on the device (image_resize.py)
     max_decoded_gib: float  # with device_resize: decoded gallery images kept in device memory between clusters, at most
+    device_resident: bool  # images (with device_resize), features and scores stay in device memory from the loader to the ranks
+    max_feature_gib: float  # with device_resident: a cluster whose query + gallery features exceed it takes the host route
 
 
 class Config(TypedDict, total=False):
@@ -64,7 +66,7 @@ class Config(TypedDict, total=False):
 MI355X_DEFAULTS: dict[str, Any] = {"dtype": "float32", "ncc_method": "auto", "max_prepared_gib": 0.0, "weights": "",
                                    "gallery_cache": "", "extractor_dtype": "float32", "f32_matrix_cores": False,
                                    "shortlist": 0, "device_resize": False, "max_decoded_gib": 8.0,
-                                   "matrix_core_peaks": False}
+                                   "matrix_core_peaks": False, "device_resident": False, "max_feature_gib": 64.0}
 
 
 def normalise(raw: dict) -> Config:
@@ -81,6 +83,11 @@ def normalise(raw: dict) -> Config:
         raise ValueError(f"[mi355x].device_resize = {extra['device_resize']!r}: expected true or false")
     if not isinstance(extra["matrix_core_peaks"], bool):
         raise ValueError(f"[mi355x].matrix_core_peaks = {extra['matrix_core_peaks']!r}: expected true or false")
+    if not isinstance(extra["device_resident"], bool):
+        raise ValueError(f"[mi355x].device_resident = {extra['device_resident']!r}: expected true or false")
+    ceiling = extra["max_feature_gib"]
+    if isinstance(ceiling, bool) or not isinstance(ceiling, (int, float)) or ceiling < 0:
+        raise ValueError(f"[mi355x].max_feature_gib = {ceiling!r}: expected a number of GiB >= 0 (0 = always the host route)")
     budget = extra["max_decoded_gib"]
     if isinstance(budget, bool) or not isinstance(budget, (int, float)) or budget < 0:
         raise ValueError(f"[mi355x].max_decoded_gib = {budget!r}: expected a number of GiB >= 0 (0 = keep nothing)")

@@ -44,13 +44,18 @@ class Dataloader:
     mode-"L" and mode-"RGB" images runs on the device (image_resize.DeviceResizer, byte-identical to Pillow), one call per
     chunk of images; every other mode goes through Pillow per image.  The decoded gallery stays in device memory, up to
     ``[mi355x] max_decoded_gib``, so later clusters - which resize the whole gallery again at their own scale - neither read
-    nor decode its files again.  ``resizer``: the DeviceResizer to use (default: one on the current GPU)."""
+    nor decode its files again.  ``resizer``: the DeviceResizer to use (default: one on the current GPU).
+
+    ``[mi355x] device_resident = true`` on top of that: a step yields ``features.DeviceImages`` instead of the two lists -
+    per output shape one dense uint8 batch in device memory, which the resize calls write directly - so the images are
+    not copied back (``to_host_list()`` gives the lists, byte for byte)."""
 
     def __init__(self, config: dict, resizer=None) -> None:
         self.config = config
         extra = config.get("mi355x", {})
         self._device_resize = bool(extra.get("device_resize", False))
         self._resizer = resizer
+        self._device_resident = self._device_resize and bool(extra.get("device_resident", False))
         if self._device_resize and resizer is None:
             from .image_resize import DeviceResizer
 
@@ -110,17 +115,12 @@ class Dataloader:
         from .image_resize import crop_box
 
         idents = [_parse_id(f, kind) for f in files]
+        if self._device_resident:
+            return self._load_images_resident(pool, files, directory, scale, crop, kind, keep), idents
         images: list[Any] = [None] * len(files)
         for c, start in enumerate(range(0, len(files), _CHUNK_IMAGES)):
             names = files[start: start + _CHUNK_IMAGES]
-            key = (str(directory), c)
-            chunk = self._kept.get(key) if keep else None
-            if chunk is None:
-                decoded = list(pool.map(lambda f: _decode_image(directory / f), names))
-                chunk = _DecodedChunk(self._resizer, decoded)
-                if keep and self._decoded_bytes + chunk.nbytes <= self._decoded_budget:
-                    self._kept[key] = chunk
-                    self._decoded_bytes += chunk.nbytes
+            chunk = self._chunk(pool, directory, names, (str(directory), c), keep)
             for where, resident in chunk.groups:
                 boxes = [crop_box(w, h, crop) for h, w in resident.shapes]
                 sizes = [(int(b[2] * scale), int(b[3] * scale)) for b in boxes]
@@ -130,6 +130,73 @@ class Dataloader:
             for k, out in zip(chunk.others, others):
                 images[start + k] = out
         return images, idents
+
+    def _chunk(self, pool, directory: Path, names, key, keep: bool):
+        chunk = self._kept.get(key) if keep else None
+        if chunk is None:
+            decoded = list(pool.map(lambda f: _decode_image(directory / f), names))
+            chunk = _DecodedChunk(self._resizer, decoded)
+            if keep and self._decoded_bytes + chunk.nbytes <= self._decoded_budget:
+                self._kept[key] = chunk
+                self._decoded_bytes += chunk.nbytes
+        return chunk
+
+    def _load_images_resident(self, pool, files, directory: Path, scale: float, crop, kind: str, keep: bool):
+        """The directory as ``features.DeviceImages``.  Output shapes are known from the files' headers (other modes: from
+        what Pillow made of them), so every shape class is allocated once and each resize call - one per (chunk, mode,
+        class) - writes its images into their rows; images of other modes are resized by Pillow as ever, uploaded, and
+        copied into their rows by the same kernels (a resize to the same size is a copy)."""
+        from .features import DeviceImages
+        from .image_resize import crop_box
+
+        dev = self._resizer.dev
+
+        def header(name):
+            with Image.open(directory / name) as image:
+                if image.mode not in ("L", "RGB"):
+                    return None
+                w, h = image.size
+            box = crop_box(w, h, crop)
+            ow, oh = int(box[2] * scale), int(box[3] * scale)
+            if ow < 1 or oh < 1:
+                raise ValueError("height and width must be > 0")  # Pillow's message for an empty target size
+            return (oh, ow) if image.mode == "L" else (oh, ow, 3)
+
+        shapes = list(pool.map(header, files))
+        other = {k: np.ascontiguousarray(_load_one(directory / files[k], files[k], scale, crop, kind)[0], dtype=np.uint8)
+                 for k, s in enumerate(shapes) if s is None}
+        for k, a in other.items():
+            DeviceImages._check_item(a)
+            shapes[k] = tuple(a.shape)
+        members: dict[tuple, list[int]] = {}
+        for k, s in enumerate(shapes):
+            members.setdefault(s, []).append(k)
+        batches = {s: dev.empty((len(idx),) + s, np.uint8) for s, idx in members.items()}
+        row = {k: r for idx in members.values() for r, k in enumerate(idx)}
+
+        def resize_into(resident, positions, boxes, sizes):
+            """``positions[i]``: the file that image i of ``resident`` is; one call per shape class among them."""
+            by_class: dict[tuple, list[int]] = {}
+            for i, k in enumerate(positions):
+                by_class.setdefault(shapes[k], []).append(i)
+            for s, select in by_class.items():
+                item = int(np.prod(s))
+                plan = self._resizer.plan(resident, boxes, sizes, select, [row[positions[i]] * item for i in select])
+                self._resizer.run(plan, resident, out=batches[s])
+
+        for c, start in enumerate(range(0, len(files), _CHUNK_IMAGES)):
+            chunk = self._chunk(pool, directory, files[start: start + _CHUNK_IMAGES], (str(directory), c), keep)
+            for where, resident in chunk.groups:
+                boxes = [crop_box(w, h, crop) for h, w in resident.shapes]
+                sizes = [(int(b[2] * scale), int(b[3] * scale)) for b in boxes]
+                resize_into(resident, [start + k for k in where], boxes, sizes)
+        for ndim in (2, 3):
+            where = [k for k, a in other.items() if a.ndim == ndim]
+            if where:
+                resident = self._resizer.upload([other[k] for k in where])
+                whole = [(0, 0, w, h) for h, w in resident.shapes]
+                resize_into(resident, where, whole, [(b[2], b[3]) for b in whole])
+        return DeviceImages(dev, len(files), [(s, idx, batches[s]) for s, idx in members.items()])
 
     # ------------------------------------------------------------------ clustering
     def _cluster_images_by_size(self, image_dir: Path, n_clusters: int) -> dict[int, list[str]]:

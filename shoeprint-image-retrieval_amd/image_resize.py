@@ -140,14 +140,22 @@ class DeviceResizer:
         return ResidentImages(self.dev.to_device(packed), offsets, [tuple(im.shape[:2]) for im in images], channels, packed.size)
 
     # ------------------------------------------------------------------ one call
-    def plan(self, resident: ResidentImages, boxes, sizes) -> ResizePlan:
-        """boxes: (x, y, w, h) per image; sizes: (out_w, out_h) per image, Pillow's order."""
+    def plan(self, resident: ResidentImages, boxes, sizes, select=None, out_offsets=None) -> ResizePlan:
+        """boxes: (x, y, w, h) per image; sizes: (out_w, out_h) per image, Pillow's order.  ``select``: the positions in
+        ``resident`` this call resizes (default all; boxes and sizes are still per image of ``resident``).  ``out_offsets``:
+        where each selected image's output starts in the output buffer, in bytes - the rows of a dense batch, say, which
+        need no alignment (features.DeviceImages); default: one behind the other at 256-byte boundaries."""
         from ._lib import ImageResizeItem
 
-        n, channels = len(resident.shapes), resident.channels
+        channels = resident.channels
+        select = range(len(resident.shapes)) if select is None else list(select)
+        n = len(select)
         items = (ImageResizeItem * max(n, 1))()
-        out_offsets, out_shapes, total = [], [], 0
-        for i, ((h, w), off, (bx, by, bw, bh), (ow, oh)) in enumerate(zip(resident.shapes, resident.offsets, boxes, sizes)):
+        dense, out_offsets, out_shapes, total = out_offsets, [], [], 0
+        for i, k in enumerate(select):
+            (h, w), off, (bx, by, bw, bh), (ow, oh) = resident.shapes[k], resident.offsets[k], boxes[k], sizes[k]
+            if dense is not None:
+                total = int(dense[i])
             if ow < 1 or oh < 1:
                 raise ValueError("height and width must be > 0")  # Pillow's message for an empty target size
             it = items[i]

@@ -165,6 +165,12 @@ def _padded(a, n: int) -> np.ndarray:
     return out
 
 
+def _require_dense(buf) -> None:
+    check = getattr(buf, "is_contiguous", None)
+    if not (check() if check is not None else buf.flags["C_CONTIGUOUS"]):
+        raise ValueError("out must be contiguous")
+
+
 # ---------------------------------------------------------------------- backbone families
 class _Family:
     """What ``Model`` needs to know about one backbone family: its C entry points (``spr_<prefix>_*``), whether it has a
@@ -531,12 +537,14 @@ class Model:
         return self._ints(self.family.fn(self.lib, "output_shape"), 3, in_h, in_w)
 
     # ------------------------------------------------------------------ forward
-    def extract_device(self, images_dev, in_channels: int = 1):
-        """uint8 device batch [N,H,W] (or [N,H,W,3]) -> float32 device features [N,C,h,w] (stays in HBM)."""
+    def extract_device(self, images_dev, in_channels: int = 1, out=None):
+        """uint8 device batch [N,H,W] (or [N,H,W,3]) -> float32 device features [N,C,h,w] (stays in HBM).  ``out``: a dense
+        device float32 [N,C,h,w] buffer to write them into (a slice of a shape class, features.FeatureSet) - the C-ABI
+        route, whose entry points take the output pointer."""
         dev, fam = self.dev, self.family
         shape = dev.shape(images_dev)
         n, h, w = shape[0], shape[1], shape[2]
-        if fam.custom_op and dev.name == "hip" and self.lib is _lib.load_library():
+        if out is None and fam.custom_op and dev.name == "hip" and self.lib is _lib.load_library():
             from . import _torch_ops
 
             if _torch_ops.enabled() and images_dev.is_contiguous() and len(shape) == (4 if in_channels == 3 else 3):
@@ -544,7 +552,12 @@ class Model:
                 return _torch_ops.load().extract(images_dev, self.packed, self.arch, self.block, [float(m) for m in self.mean],
                                                  [float(s) for s in self.std], _COMPUTE[self.compute])
         c, oh, ow = self.output_shape(h, w)
-        out = dev.empty((n, c, oh, ow), np.float32)
+        if out is None:
+            out = dev.empty((n, c, oh, ow), np.float32)
+        elif tuple(dev.shape(out)) != (n, c, oh, ow):
+            raise ValueError(f"out is {tuple(dev.shape(out))}, the features are {(n, c, oh, ow)}")
+        else:
+            _require_dense(out)
         ws = dev.empty_bytes(max(16, fam.fn(self.lib, "workspace_bytes")(self.handle, n, h, w)))
         mean = (C.c_float * 3)(*self.mean)
         inv_std = (C.c_float * 3)(*[np.float32(1.0) / np.float32(s) for s in self.std])
@@ -661,6 +674,40 @@ class Model:
                 if progress:
                     print(f"\rfeatures {done}/{len(images)}", end="" if done < len(images) else "\n", file=sys.stderr)
         return results
+
+    def get_multiple_feature_maps_device(self, images, progress: bool = True):
+        """``get_multiple_feature_maps`` that leaves the features in HBM: a ``features.FeatureSet`` whose ``to_host_list()``
+        is that function's result, bit for bit.  ``images``: a host list as there, or ``features.DeviceImages`` (the loader's
+        device-resident output: nothing is uploaded).  CLAHE and extraction run per image shape class in ``batch_size``
+        pieces, each piece written straight into its slice of the feature class; image classes whose features share a shape
+        lie one behind the other in one feature class.  Nothing is copied to the host."""
+        from .features import DeviceImages, FeatureSet
+
+        dev = self.dev
+        if not isinstance(images, DeviceImages):
+            images = DeviceImages.from_host(dev, images)
+        total, done = len(images), 0
+        # feature shape -> [(image class, first row in the feature class)], in order of first appearance
+        layout: dict[tuple, list] = {}
+        rows: dict[tuple, int] = {}
+        for k, (shape, idx, _) in enumerate(images.classes):
+            fshape = tuple(self.output_shape(shape[0], shape[1]))
+            layout.setdefault(fshape, []).append((k, rows.get(fshape, 0)))
+            rows[fshape] = rows.get(fshape, 0) + len(idx)
+        classes = []
+        for fshape, parts in layout.items():
+            feats = dev.empty((rows[fshape],) + fshape, np.float32)
+            for k, row0 in parts:
+                shape, idx, batch = images.classes[k]
+                for start in range(0, len(idx), self.batch_size):
+                    n = min(self.batch_size, len(idx) - start)
+                    self.extract_device(self.clahe_device(dev.narrow0(batch, start, n)), in_channels=3 if len(shape) == 3 else 1,
+                                        out=dev.narrow0(feats, row0 + start, n))
+                    done += n
+                    if progress:
+                        print(f"\rfeatures {done}/{total}", end="" if done < total else "\n", file=sys.stderr)
+            classes.append((fshape, np.concatenate([images.classes[k][1] for k, _ in parts]), feats))
+        return FeatureSet(dev, total, classes)
 
     def close(self):
         if getattr(self, "handle", None):

@@ -98,6 +98,34 @@ def _host_items(dev, maps) -> list:
     return list(dev.to_host(batch)) if items is None else items
 
 
+class _HostSide:
+    """A host item list behind the interface ``_blocks`` walks (``features.FeatureSet`` is the resident one)."""
+
+    def __init__(self, dev, items):
+        self.dev, self.items = dev, items
+
+    def __len__(self) -> int:
+        return len(self.items)
+
+    def groups(self, used=None) -> dict[tuple, list[int]]:
+        return _group_by_shape(self.items, used)
+
+    def stack(self, lib, idx, storage: str | None = None):
+        buf = self.dev.stack_to_device([self.items[i] for i in idx])
+        return buf if storage is None else self.dev.astype_storage(buf, storage)
+
+
+def _is_resident(maps) -> bool:
+    from .features import FeatureSet
+
+    return isinstance(maps, FeatureSet)
+
+
+def _side(dev, maps):
+    """Any accepted input as a side of the walk: a FeatureSet as it is (nothing is copied), everything else as a host list."""
+    return maps if _is_resident(maps) or isinstance(maps, _HostSide) else _HostSide(dev, _host_items(dev, maps))
+
+
 class NccScorer:
     """Scores queries against a gallery with the HIP NCC kernels; everything stays in HBM.
 
@@ -320,24 +348,31 @@ class NccScorer:
 
     # ------------------------------------------------------------------ list-of-arrays level
     def _blocks(self, q_items, g_items, rotations, scales, q_used=None, g_used=None):
-        """THE walk over ragged host item lists, behind ``score_matrix``, ``score_matrix_located`` and ``locate``: grouping by
+        """THE walk over ragged item sets (``_side``: host lists or resident ``FeatureSet``s, either per side), behind
+        ``score_matrix``, ``score_matrix_located`` and ``locate``: grouping by
         shape, variant lists, plans, chunk budget and gallery preparation are decided here and nowhere else.  Of the items
         ``q_used`` / ``g_used`` (ascending indices; default all) every query shape class is stacked, uploaded, expanded by
         ``VariantBuilder.variants`` and cast to the storage type once; every gallery shape class gets one plan per distinct
         variant shape (the 1/sigma map depends on the template size) and goes chunk by chunk, the prepared forms of a chunk -
         one per plan, all alive while the query classes are walked - sharing the budget.  Yields per (gallery chunk, query
         class) a ``_Block``; its ``prepared(vs)`` uploads the chunk on first need and prepares it once per variant shape, so a
-        block the consumer passes over costs nothing.  A block is good until the walk is advanced."""
+        block the consumer passes over costs nothing.  A block is good until the walk is advanced.  A resident side is never
+        copied to the host: its stacks are spr_items_gather calls (``FeatureSet.stack``), the cast to the storage type fused
+        into the gallery chunks' and, without variants, the query classes'."""
         from .variants import VariantBuilder
 
         if self._variants is None:
             self._variants = VariantBuilder(self.lib, self.dev)  # (keeps its resample tables on the device)
         q_side = []
-        for qshape, q_idx in _group_by_shape(q_items, q_used).items():
-            batches = self._variants.variants(self.dev.stack_to_device([q_items[i] for i in q_idx]), rotations, scales)
+        plain = rotations is None and scales is None
+        for qshape, q_idx in q_items.groups(q_used).items():
+            if plain and _is_resident(q_items):  # no float32 intermediate to expand: gathered and cast in one pass
+                q_side.append((qshape, q_idx, [(0, tuple(qshape[1:]), q_items.stack(self.lib, q_idx, self.storage))]))
+                continue
+            batches = self._variants.variants(q_items.stack(self.lib, q_idx), rotations, scales)
             q_side.append((qshape, q_idx, [(number, tuple(self.dev.shape(v)[2:]), self.dev.astype_storage(v, self.storage))
                                            for number, v in enumerate(batches)]))
-        for gshape, g_idx in _group_by_shape(g_items, g_used).items():
+        for gshape, g_idx in g_items.groups(g_used).items():
             plans = {}
             for qshape, _, variants in q_side:
                 if qshape[0] != gshape[0]:
@@ -352,8 +387,7 @@ class NccScorer:
                 def prepared(vs):
                     if vs not in alive:
                         if None not in alive:
-                            alive[None] = self.dev.astype_storage(self.dev.stack_to_device([g_items[i] for i in idx]),
-                                                                  self.storage)
+                            alive[None] = g_items.stack(self.lib, idx, self.storage)
                         alive[vs] = self.prepare_gallery(plans[vs], alive[None])
                     return alive[vs]
 
@@ -374,7 +408,7 @@ class NccScorer:
     def _locate(self, shoemark_maps, shoeprint_maps, pairs, rotations, scales):
         """``locate`` plus the cropped size (th, tw) int32 [P,2] of every pair's winning variant template, read off the
         variant batches themselves."""
-        q_items, g_items = _host_items(self.dev, shoemark_maps), _host_items(self.dev, shoeprint_maps)
+        q_items, g_items = _side(self.dev, shoemark_maps), _side(self.dev, shoeprint_maps)
         pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
         n = len(pairs)
         best = np.full(n, -np.inf, dtype=np.float32)
@@ -412,7 +446,8 @@ class NccScorer:
         matrix keeps the running maximum over variants (similarity.py:357-367)."""
         q_items, q_dev = _as_item_list(shoemark_maps)
         g_items, g_dev = _as_item_list(shoeprint_maps)
-        if q_items is None and g_items is None and rotations is None and scales is None:
+        resident = _is_resident(shoemark_maps) or _is_resident(shoeprint_maps)
+        if q_items is None and g_items is None and rotations is None and scales is None and not resident:
             return self.dev.to_host(self.scores_device(q_dev, g_dev))
         return self._walk(shoemark_maps, shoeprint_maps, accumulate_into, rotations, scales, False)[0]
 
@@ -437,10 +472,10 @@ class NccScorer:
 
     def _walk(self, shoemark_maps, shoeprint_maps, accumulate_into, rotations, scales, located: bool,
               fill_unfused: bool = True):
-        """The scoring consumer of ``_blocks`` behind ``score_matrix`` (``located`` False: plain spr_ncc_score launches, the
-        last three results are None) and ``score_matrix_located``: (scores, variant, yx, t_hw).  Every block is scored into a
-        device matrix of its own, all variants in ascending number through accumulate_max, and folded into the host matrix."""
-        q_items, g_items = _host_items(self.dev, shoemark_maps), _host_items(self.dev, shoeprint_maps)
+        """The host form of the scoring walk behind ``score_matrix`` (``located`` False: plain spr_ncc_score launches, the
+        last three results are None) and ``score_matrix_located``: (scores, variant, yx, t_hw).  ``_walk_device`` folds the
+        blocks on the device; the finished matrices come down once each."""
+        q_items, g_items = _side(self.dev, shoemark_maps), _side(self.dev, shoeprint_maps)
         nq, ng = len(q_items), len(g_items)
         out = np.zeros((nq, ng), dtype=np.float32) if accumulate_into is None else accumulate_into
         variant = yx = t_hw = None
@@ -450,18 +485,54 @@ class NccScorer:
             variant = np.full((nq, ng), -1, dtype=np.int32)
             yx = np.full((nq, ng, 2), -1, dtype=np.int32)
             t_hw = np.zeros((nq, len(variant_labels(rotations, scales)), 2), dtype=np.int32)
-            second_pass = []  # blocks (query indices, gallery indices) one of whose plans has no peak form
         if nq == 0 or ng == 0:
             return out, variant, yx, t_hw
+        s_dev, tag_dev, packed_dev, t_hw, second_pass = self._walk_device(q_items, g_items, rotations, scales, located)
+        out[...] = np.maximum(out, self.dev.to_host(s_dev))
+        if located:
+            variant[...] = self.dev.to_host(tag_dev)
+            yx[...] = _unpack_yx(self.dev.to_host(packed_dev))
+        if located and second_pass and fill_unfused:
+            self._fill_unfused(q_items, g_items, second_pass, rotations, scales, out, variant, yx)
+        return out, variant, yx, t_hw
+
+    def _fill_unfused(self, q_items, g_items, second_pass, rotations, scales, out, variant, yx) -> None:
+        """The second pass over the blocks of plans without a peak form: ``locate`` on every pair of them, written into the
+        host matrices where the floored score is above 0 (as the fused form: no position where it is 0)."""
+        pairs = np.array([(q, g) for q_idx, idx in second_pass for q in q_idx for g in idx], dtype=np.int64)
+        _, p_variant, p_yx, _ = self._locate(q_items, g_items, pairs, rotations, scales)
+        hit = out[pairs[:, 0], pairs[:, 1]] > 0
+        variant[pairs[hit, 0], pairs[hit, 1]] = p_variant[hit]
+        yx[pairs[hit, 0], pairs[hit, 1]] = p_yx[hit]
+
+    def _walk_device(self, q_items, g_items, rotations, scales, located: bool):
+        """The scoring consumer of ``_blocks``: device (scores float32 [Q,G], variant int32 [Q,G], packed position int32
+        [Q,G] - ``(y << 16) | x``, -1 = none), the host t_hw, and the blocks (query indices, gallery indices) one of whose
+        plans has no peak form, which stay at variant -1 / position -1.  Every block is scored into a device matrix of its
+        own, all variants in ascending number through accumulate_max, and folded into the [Q,G] matrices by
+        spr_block_scatter: its query and gallery indices are each distinct and every cell belongs to one block."""
+        dev = self.dev
+        nq, ng = len(q_items), len(g_items)
+        scores = dev.zeros((nq, ng), np.float32)
+        tag = packed = t_hw = None
+        second_pass = []
+        if located:
+            from .variants import variant_labels
+
+            tag = dev.to_device(np.full((nq, ng), -1, dtype=np.int32))
+            packed = dev.to_device(np.full((nq, ng), -1, dtype=np.int32))
+            t_hw = np.zeros((nq, len(variant_labels(rotations, scales)), 2), dtype=np.int32)
+        if nq == 0 or ng == 0:
+            return scores, tag, packed, t_hw, second_pass
         for b in self._blocks(q_items, g_items, rotations, scales):
             q_idx, idx = b.q_idx, b.g_idx
             self.last_chunk_items = b.chunk_items  # (read by the tests)
-            sub = self.dev.zeros((len(q_idx), len(idx)), np.float32)
+            sub = dev.zeros((len(q_idx), len(idx)), np.float32)
             fused = located and all(b.plans[vs].has_peaks for _, vs, _ in b.variants)
             sub_yx = sub_tag = None
             if fused:
-                sub_yx = self.dev.to_device(np.full((len(q_idx), len(idx)), -1, dtype=np.int32))
-                sub_tag = self.dev.to_device(np.full((len(q_idx), len(idx)), -1, dtype=np.int32))
+                sub_yx = dev.to_device(np.full((len(q_idx), len(idx)), -1, dtype=np.int32))
+                sub_tag = dev.to_device(np.full((len(q_idx), len(idx)), -1, dtype=np.int32))
             elif located:
                 second_pass.append((q_idx, idx))
             for number, vs, v in b.variants:
@@ -471,19 +542,47 @@ class NccScorer:
                 pg = b.prepared(vs)
                 self.score_prepared(plan, self.prepare_queries(plan, v), len(q_idx), pg, len(idx), sub, len(idx), 0,
                                     accumulate_max=True, peaks=sub_yx, tags=sub_tag, tag=number)
-            out[np.ix_(q_idx, idx)] = np.maximum(out[np.ix_(q_idx, idx)], self.dev.to_host(sub))
-            if fused:
-                packed = self.dev.to_host(sub_yx).astype(np.int32, copy=False)
-                variant[np.ix_(q_idx, idx)] = self.dev.to_host(sub_tag)
-                yx[np.ix_(q_idx, idx)] = np.where((packed < 0)[..., None], -1,
-                                                 np.stack([packed >> 16, packed & 0xFFFF], axis=-1))
-        if located and second_pass and fill_unfused:
-            pairs = np.array([(q, g) for q_idx, idx in second_pass for q in q_idx for g in idx], dtype=np.int64)
-            _, p_variant, p_yx, _ = self._locate(q_items, g_items, pairs, rotations, scales)
-            hit = out[pairs[:, 0], pairs[:, 1]] > 0  # (as the fused form: no position where the floored score is 0)
-            variant[pairs[hit, 0], pairs[hit, 1]] = p_variant[hit]
-            yx[pairs[hit, 0], pairs[hit, 1]] = p_yx[hit]
-        return out, variant, yx, t_hw
+            rows = dev.to_device(np.asarray(q_idx, dtype=np.int32))
+            cols = dev.to_device(np.asarray(idx, dtype=np.int32))
+            for dst, src, mode in ((scores, sub, 1), (tag, sub_tag, 0), (packed, sub_yx, 0)):
+                if src is not None:
+                    self.lib.check(self.lib.spr_block_scatter(dev.ptr(dst), ng, dev.ptr(src), len(idx), dev.ptr(rows),
+                                                              len(q_idx), dev.ptr(cols), len(idx), mode, dev.stream()))
+        return scores, tag, packed, t_hw, second_pass
+
+    def score_matrix_device(self, q, g, rotations=None, scales=None, located: bool = False):
+        """``score_matrix`` that leaves its result in HBM: the device float32 [Q,G] matrix of any accepted inputs (host
+        lists or ``FeatureSet``s, either per side).  With ``located`` also, as ``score_matrix_located``, the device int32
+        [Q,G] variant numbers and packed positions ``(y << 16) | x`` (-1 where the score is 0) and the host t_hw int32
+        [Q,V,2]: ``(scores, variant, packed_yx, t_hw)``.  Blocks of plans without a peak form are located by the second pass
+        of ``locate``, which needs the host copy of the scores to know where they are above 0: such a scorer pays one
+        transfer of the matrix down and of the two int32 matrices up."""
+        q_items, g_items = _side(self.dev, q), _side(self.dev, g)
+        s_dev, tag, packed, t_hw, second_pass = self._walk_device(q_items, g_items, rotations, scales, located)
+        if not located:
+            return s_dev
+        if second_pass:
+            out, variant, yx = self.dev.to_host(s_dev), self.dev.to_host(tag), _unpack_yx(self.dev.to_host(packed))
+            self._fill_unfused(q_items, g_items, second_pass, rotations, scales, out, variant, yx)
+            tag = self.dev.to_device(variant)
+            packed = self.dev.to_device(np.where(variant < 0, -1, (yx[..., 0] << 16) | yx[..., 1]).astype(np.int32))
+        return s_dev, tag, packed, t_hw
+
+    def cells_device(self, matrix, ld: int, qs, gs) -> np.ndarray:
+        """Host copy of the 4-byte cells ``matrix[qs[i], gs[i]]`` of a dense device [Q, ld] matrix (float32 or int32; the
+        result has the bits as int32): one spr_items_gather of one-element items, so a shortlist's entries come down and not
+        the matrix."""
+        dev = self.dev
+        flat = np.asarray(qs, dtype=np.int64) * int(ld) + np.asarray(gs, dtype=np.int64)
+        if len(flat) == 0:
+            return np.zeros(0, dtype=np.int32)
+        if flat.max() >= 2 ** 31:
+            raise ValueError("matrix too large for a 32-bit cell index")
+        out = dev.empty((len(flat),), np.int32)
+        index = dev.to_device(flat.astype(np.int32))
+        self.lib.check(self.lib.spr_items_gather(dev.ptr(matrix), 1, dev.ptr(index), len(flat), dev.ptr(out), _lib.F32,
+                                                 dev.stream()))
+        return dev.to_host(out).astype(np.int32, copy=False)
 
     def multi_layer_scores_device(self, layers, out=None):
         """Device [Q,G] float32 mean over feature layers of the per-layer score matrices (e.g.
@@ -514,7 +613,12 @@ class NccScorer:
         nq, ng = scores_host.shape
         if nq == 0:
             return np.zeros(0, dtype=np.int32)
-        s_dev = self.dev.to_device(np.ascontiguousarray(scores_host, dtype=np.float32))
+        return self.ranks_of_device(self.dev.to_device(np.ascontiguousarray(scores_host, dtype=np.float32)), matching_pairs)
+
+    def ranks_of_device(self, s_dev, matching_pairs: Sequence[int]) -> np.ndarray:
+        """``ranks`` of a score matrix that is already in HBM (``score_matrix_device``): only the rank vector comes down."""
+        if self.dev.shape(s_dev)[0] == 0:
+            return np.zeros(0, dtype=np.int32)
         m_dev = self.dev.to_device(np.asarray(matching_pairs, dtype=np.int32))
         ranks = self.dev.to_host(self.ranks_device(s_dev, m_dev)).astype(np.int32, copy=True)
         if (ranks == 0).any():
@@ -528,6 +632,12 @@ def _require_contiguous(buf, name: str) -> None:
     check = getattr(buf, "is_contiguous", None)
     if not (check() if check is not None else buf.flags["C_CONTIGUOUS"]):
         raise ValueError(f"{name} must be contiguous")
+
+
+def _unpack_yx(packed) -> np.ndarray:
+    """Packed positions ``(y << 16) | x`` -> int32 [..., 2]; -1 (no position) -> (-1, -1)."""
+    packed = np.asarray(packed).astype(np.int32, copy=False)
+    return np.where((packed < 0)[..., None], -1, np.stack([packed >> 16, packed & 0xFFFF], axis=-1)).astype(np.int32)
 
 
 def _group_by_shape(items, used=None) -> dict[tuple, list[int]]:
@@ -610,8 +720,13 @@ def compare_maps(
     comp = config["comparison"]
     rotations, scales = comp.get("rotations"), comp.get("scales")
     scorer = scorer or scorer_from_config(config)
-    scores = scorer.score_matrix(shoemark_maps, shoeprint_maps, rotations=rotations, scales=scales)
-    ranks = scorer.ranks(scores, matching_pairs)
+    if _is_resident(shoemark_maps) and _is_resident(shoeprint_maps):
+        # features.FeatureSet on both sides: the matrix is ranked where it was folded, only the rank vector comes down
+        ranks = scorer.ranks_of_device(scorer.score_matrix_device(shoemark_maps, shoeprint_maps, rotations, scales),
+                                       matching_pairs)
+    else:
+        scores = scorer.score_matrix(shoemark_maps, shoeprint_maps, rotations=rotations, scales=scales)
+        ranks = scorer.ranks(scores, matching_pairs)
     if progress:
         for i, r in enumerate(ranks):
             print(f"Print {i} true match ranked {r}")  # similarity.py:375
@@ -642,7 +757,10 @@ def retrieve(
     """The ``k`` best gallery items of every query (1 <= k <= 256), best first in the ranker's order, and - with
     ``locate`` - for each of them the best query variant, the peak of its NCC map and the offset
     ``(y - th//2, x - tw//2)`` at which the cropped ``th x tw`` variant template lies on the cropped gallery map.
-    ``config["comparison"]`` supplies rotations and scales as for ``compare_maps``."""
+    ``config["comparison"]`` supplies rotations and scales as for ``compare_maps``.  With a ``features.FeatureSet`` on both
+    sides the score matrix never leaves HBM (``retrieve_resident``)."""
+    if _is_resident(shoemark_maps) and _is_resident(shoeprint_maps):
+        return retrieve_resident(shoemark_maps, shoeprint_maps, config, k, locate=locate, scorer=scorer)[1]
     return retrieve_with_scores(shoemark_maps, shoeprint_maps, config, k, locate=locate, scorer=scorer)[1]
 
 
@@ -653,10 +771,14 @@ def retrieve_with_scores(shoemark_maps, shoeprint_maps, config: dict, k: int = 1
     (run_mi355x.py).  With ``locate`` the pass is ``score_matrix_located``'s list-of-arrays walk - device-resident
     batches are copied to the host and uploaded again by shape group, where ``locate=False`` keeps ``score_matrix``'s
     device route - and blocks of plans without a peak form are not filled: their shortlisted pairs, Q*k of them, go
-    through the second pass as entries with score 0 do."""
+    through the second pass as entries with score 0 do.  ``features.FeatureSet``s on both sides stay in HBM throughout
+    (``retrieve_resident``); the matrix comes down once, because it is returned."""
     comp = config["comparison"]
     rotations, scales = comp.get("rotations"), comp.get("scales")
     scorer = scorer or scorer_from_config(config)
+    if _is_resident(shoemark_maps) and _is_resident(shoeprint_maps):
+        s_dev, short = retrieve_resident(shoemark_maps, shoeprint_maps, config, k, locate=locate, scorer=scorer)
+        return scorer.dev.to_host(s_dev), short
     if not locate:
         scores = scorer.score_matrix(shoemark_maps, shoeprint_maps, rotations=rotations, scales=scales)
         return scores, _shortlist(scorer, shoemark_maps, shoeprint_maps, scores, k, False, rotations, scales)
@@ -664,15 +786,35 @@ def retrieve_with_scores(shoemark_maps, shoeprint_maps, config: dict, k: int = 1
     return scores, _shortlist(scorer, shoemark_maps, shoeprint_maps, scores, k, True, rotations, scales, located=located)
 
 
-def _shortlist(scorer: NccScorer, shoemark_maps, shoeprint_maps, scores: np.ndarray, k: int, locate: bool, rotations,
-               scales, located=None) -> Shortlist:
+def retrieve_resident(shoemark_maps, shoeprint_maps, config: dict, k: int = 10, *, locate: bool = True,
+                      scorer: NccScorer | None = None):
+    """``retrieve_with_scores`` for ``features.FeatureSet``s that leaves the matrix where it is: (device float32 [Q,G]
+    scores, Shortlist).  The top k are taken from the device matrix and the shortlisted entries' variant and position are
+    gathered from the device matrices; what comes down is the Shortlist's own arrays (and ``locate``'s per-pair results for
+    entries the scoring pass has no position for)."""
+    comp = config["comparison"]
+    rotations, scales = comp.get("rotations"), comp.get("scales")
+    scorer = scorer or scorer_from_config(config)
+    if not locate:
+        s_dev = scorer.score_matrix_device(shoemark_maps, shoeprint_maps, rotations, scales)
+        return s_dev, _shortlist(scorer, shoemark_maps, shoeprint_maps, s_dev, k, False, rotations, scales, resident=True)
+    q_items, g_items = _side(scorer.dev, shoemark_maps), _side(scorer.dev, shoeprint_maps)
+    s_dev, *located = scorer._walk_device(q_items, g_items, rotations, scales, True)[:4]  # (unfused blocks: not filled)
+    return s_dev, _shortlist(scorer, shoemark_maps, shoeprint_maps, s_dev, k, True, rotations, scales, located=located,
+                             resident=True)
+
+
+def _shortlist(scorer: NccScorer, shoemark_maps, shoeprint_maps, scores, k: int, locate: bool, rotations,
+               scales, located=None, resident: bool = False) -> Shortlist:
     """``retrieve`` behind its score matrix: ``scores`` is what ``scorer.score_matrix`` gave for these maps and variants
     (run_mi355x.py ranks from the same matrix instead of scoring twice).  ``located`` = the (variant, yx, t_hw) that
     ``scorer._score_matrix_located`` gave beside ``scores``: the shortlisted entries are gathered from them, and only those
     whose score is 0 - the scoring pass has no position for them - go through the second pass of ``NccScorer.locate``, which
-    gives the un-floored peak (without ``located``: all of them)."""
+    gives the un-floored peak (without ``located``: all of them).  ``resident``: ``scores`` is the device matrix of
+    ``score_matrix_device`` instead, ``located`` its device (variant, packed position) matrices and the host t_hw:
+    nothing is uploaded again and only the shortlisted cells come down (``NccScorer.cells_device``)."""
     dev = scorer.dev
-    top_s, top_i = scorer.topk_device(dev.to_device(np.ascontiguousarray(scores, dtype=np.float32)), k)
+    top_s, top_i = scorer.topk_device(scores if resident else dev.to_device(np.ascontiguousarray(scores, dtype=np.float32)), k)
     out = Shortlist(dev.to_host(top_i).astype(np.int32, copy=True), dev.to_host(top_s).astype(np.float32, copy=True),
                     None, None, None)
     if not locate:
@@ -691,8 +833,13 @@ def _shortlist(scorer: NccScorer, shoemark_maps, shoeprint_maps, scores: np.ndar
 
     if located is not None:
         all_variant, all_yx, all_t_hw = located
-        variant = all_variant[qs, gs]
-        put(qs, ps, variant, all_yx[qs, gs], all_t_hw[qs, np.maximum(variant, 0)])
+        if resident:
+            ng = dev.shape(scores)[1]
+            variant = scorer.cells_device(all_variant, ng, qs, gs)
+            cell_yx = _unpack_yx(scorer.cells_device(all_yx, ng, qs, gs))
+        else:
+            variant, cell_yx = all_variant[qs, gs], all_yx[qs, gs]
+        put(qs, ps, variant, cell_yx, all_t_hw[qs, np.maximum(variant, 0)])
         rest = variant < 0
         qs, ps, gs = qs[rest], ps[rest], gs[rest]
         if len(qs) == 0:
