@@ -19,7 +19,7 @@
 //     prep kernel scales query column k by (1 - i w^k):  Z[k] = i cot(pi k/96 + pi/4) Y'[k] + conj(Y'[48-k]).
 //   * accumulators: 24 per lane (40 in the 256-lane kernel), 1/sigma slice 36.9 KB per channel (40.9).
 //
-// LDS per workgroup (151 KB): per pair {image 48 x 139 complex | per-wave exchange rows | Nyquist columns},
+// LDS per workgroup (145 KB): per pair {image 48 x 139 complex | per-wave exchange rows | Nyquist products},
 // shared {column twiddles | pre-twist table}.
 #include <cstdlib>
 
@@ -117,7 +117,8 @@ struct Six {
   static constexpr int kImgBytes = C::COLS * RS * 8;
   static constexpr int kXbOff = kImgOff + kImgBytes;
   static constexpr int kNyqOff = kXbOff + WAVES * kXbWave * 8;
-  static constexpr int kHalfBytes = kNyqOff + 2 * 2 * C::NH * 8;  // two buffers of Nyquist columns (see the channel loop)
+  static constexpr int kNyqBuf = C::NH;  // one buffer: the products of the two sides' Nyquist columns
+  static constexpr int kHalfBytes = kNyqOff + 2 * kNyqBuf * 8;  // two such buffers (see the channel loop)
   // ... and shared by both
   static constexpr int kRedOff = 2 * kHalfBytes;  // 2 x 8 floats of reduction scratch, then 2 barrier counters,
   static constexpr int kPeakOff = kRedOff + 128;  // then 2 x 8 peak positions (the peak form's second word per wave)
@@ -130,8 +131,9 @@ struct Six {
 };
 
 // PEAKS: the form behind spr_ncc_score_peaks is its own instantiation - the kernel is register-tight, and the plain form
-// carries nothing of it.  Only the epilogue differs.
-template <class C, bool PEAKS>
+// carries nothing of it.  Only the epilogue differs.  MAPS: the form behind spr_ncc_maps, likewise - its stores sit inside the
+// accumulation of the row pass, where even a not-taken branch per accumulator set cuts the scoring forms into basic blocks.
+template <class C, bool PEAKS, bool MAPS>
 __global__ void __launch_bounds__(2 * C::NT, 3)
 pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_bytes,
              const unsigned char* __restrict__ pg, size_t g_item_bytes, float* __restrict__ scores, long long ld,
@@ -162,10 +164,9 @@ pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_by
   unsigned char* hl = lds + half * S::kHalfBytes;
   float* red = reinterpret_cast<float*>(lds + S::kRedOff) + half * 8;
   unsigned* bar = reinterpret_cast<unsigned*>(lds + S::kRedOff + 64) + half * 8;  // this pair's barrier counter
-  unsigned* nlive_p = bar + 2;                                                   // its number of live channels
   unsigned bar_target = 0;
   cf* R = reinterpret_cast<cf*>(hl + S::kImgOff);
-  cf* nyq = reinterpret_cast<cf*>(hl + S::kNyqOff);      // [buffer][0, NH): gallery column nw/2, [NH, 2NH): query's
+  cf* nyq = reinterpret_cast<cf*>(hl + S::kNyqOff);      // [buffer][0, NH): column nw/2 of the product spectrum
   cf* twt_h = reinterpret_cast<cf*>(lds + S::kTwOff);    // w_NH^(+t p) at [p][t]
   cf* ctab2 = reinterpret_cast<cf*>(lds + S::kCtabOff);  // pre-twist cotangents, {c(a), c(a+1)} at [a/2][t]
   unsigned short* chan = reinterpret_cast<unsigned short*>(lds + S::kListOff) + half * g.channels;
@@ -189,20 +190,38 @@ pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_by
   // A channel that is constant (all zero after ReLU, typically) in the query or in the gallery item contributes exactly
   // 0 to every position (similarity.py:68-70: 0/0 -> NaN -> 0) while still counting in the divisor: the prep kernels
   // flag such channels per item, and the pair walks the list of channels live on BOTH sides.
-  for (int k = tid0; k < g.channels; k += NT)
-    chan[k] = (q_item[g.q_flags_off + k] | g_item[g.g_flags_off + k]) ? 0xFFFFu : static_cast<unsigned short>(k);
-  __syncthreads();
-  if (tid0 == 0) {  // in-place compaction, in channel order (the write index never passes the read index)
-    int n = 0;
-    for (int k = 0; k < g.channels; ++k) {
-      const unsigned short v = chan[k];
-      if (v != 0xFFFFu) chan[n++] = v;
+  // Order-preserving compaction, a stretch of NT channels at a time: a lane takes one channel, its place among the wave's
+  // live ones is the number of set bits below its own in the wave's 64-bit mask (gathered with shfl_xor), the waves'
+  // totals meet in the reduction scratch.  Nothing reads the list before the barrier that follows.
+  int n_before = 0;
+  {
+    int* tot = reinterpret_cast<int*>(red);
+    const int ln = tid0 & 63;
+    for (int k0 = 0; k0 < g.channels; k0 += NT) {
+      const int k = k0 + tid0;
+      const bool alive = k < g.channels && !(q_item[g.q_flags_off + k] | g_item[g.g_flags_off + k]);
+      int lo = alive && ln < 32 ? static_cast<int>(1u << ln) : 0, hi = alive && ln >= 32 ? static_cast<int>(1u << (ln - 32)) : 0;
+      for (int m = 1; m < 64; m <<= 1) {
+        lo |= shfl_xor(lo, m);
+        hi |= shfl_xor(hi, m);
+      }
+      const unsigned below_lo = ln < 32 ? (1u << ln) - 1u : 0xFFFFFFFFu, below_hi = ln < 32 ? 0u : (1u << (ln - 32)) - 1u;
+      const int before = __builtin_popcount(static_cast<unsigned>(lo) & below_lo) + __builtin_popcount(static_cast<unsigned>(hi) & below_hi);
+      if (k0 > 0) __syncthreads();  // (the previous stretch's totals have been read)
+      if (ln == 0) tot[wv] = __builtin_popcount(static_cast<unsigned>(lo)) + __builtin_popcount(static_cast<unsigned>(hi));
+      __syncthreads();
+      int at = n_before + before;
+      for (int w = 0; w < S::WAVES; ++w) {
+        const int t = tot[w];
+        at += w < wv ? t : 0;
+        n_before += t;
+      }
+      if (alive) chan[at] = static_cast<unsigned short>(k);
     }
-    if (n == 0) chan[0] = 0;  // (nothing live: the loop below does not run; the prologue's loads still need an address)
-    *nlive_p = static_cast<unsigned>(n);
+    if (n_before == 0 && tid0 == 0) chan[0] = 0;  // (nothing live: the loop below does not run; the prologue's loads still need an address)
   }
   __syncthreads();
-  const int nlive = uniform(static_cast<int>(*nlive_p));
+  const int nlive = uniform(n_before);
   const int last_i = nlive > 0 ? nlive - 1 : 0;
   auto chan_at = [&](int i) { return static_cast<int>(chan[i < last_i ? i : last_i]); };  // (prefetches past the end re-read)
 
@@ -210,8 +229,7 @@ pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_by
   // Buffer loads: descriptor = one prepared item, lane offset = 16 * lane of the pair, the rest (channel, column
   // round, register) is a scalar offset.
   float4 nxt[2 * H2];  // operands of the next column unit: H2 x (2 complex of G), H2 x (2 complex of Q)
-  cf nyq_g, nyq_q;     // (every lane loads both sides' Nyquist value and keeps its own: a select between two resource
-                       // descriptors would put the load into a waterfall loop)
+  cf nyq_g, nyq_q;     // (every lane loads both sides' Nyquist value, the lower half of the pair stores their product)
   const BufRsrc g_rs = make_rsrc(g_item, g_item_bytes), q_rs = make_rsrc(q_item, q_item_bytes);
   const unsigned voff16 = static_cast<unsigned>(tid0) * 16u;
   const unsigned voff_nyq = static_cast<unsigned>(tid0 % C::NH) * 8u + C::kNyqOffset * 8u;
@@ -252,11 +270,17 @@ pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_by
   for (int pp = 0; pp < 6; ++pp) acc[pp][0] = acc[pp][1] = cmake(0.0f, 0.0f);
 
   // ---- prologue ---------------------------------------------------------------------------------------------------------
-  issue_nyq(chan_at(0));
-  nyq[tid0] = tid0 < C::NH ? nyq_g : nyq_q;
-  issue_nyq(chan_at(1));
-  nyq[NT + tid0] = tid0 < C::NH ? nyq_g : nyq_q;
-  issue_unit(chan_at(0), 0);
+  // Channel numbers travel in scalar registers (or the Nyquist loads, whose offset they enter, run in waterfall loops):
+  // this live channel and the next two; the one after those is read from the list during the row pass.
+  int sc0 = uniform(chan_at(0)), sc1 = uniform(chan_at(1)), sc2 = uniform(chan_at(2));
+  auto store_nyq = [&](int buf, int lane_of_pair) {
+    if (lane_of_pair < C::NH) nyq[buf * S::kNyqBuf + lane_of_pair] = cmul(nyq_g, nyq_q);
+  };
+  issue_nyq(sc0);
+  store_nyq(0, tid0);
+  issue_nyq(sc1);
+  store_nyq(1, tid0);
+  issue_unit(sc0, 0);
   __syncthreads();
 
   // The channel loop, per wave (A, B = its unit - four image columns - of column round 0 / 1; the LDS reads of an
@@ -272,10 +296,12 @@ pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_by
   //   B1  every image column of this channel is stored - before the row pass reads the image;
   //   B2  every wave has finished reading the image of the previous channel - before the first LDS store of this one; it
   //       sits behind part 1 of A (registers only), so a wave that leaves the row pass early has work before it waits.
-  // The Nyquist values of the live channel after next are loaded during this channel and stored to LDS at its end, i.e.
-  // before the next B2; wave 0 reads them in its part 1 two channels on: two buffers.
+  // The Nyquist values of the live channel after next are loaded during this channel and their product is stored to LDS at
+  // its end, i.e. before the next B2; wave 0 adds it to its product spectrum two channels on: two buffers.  (Factors in LDS
+  // and the multiplication on wave 0 made that wave the last of its pair at B2: 24 reads and 12 multiplications more than
+  // the other five, ahead of unit B's loads.)
   for (int ci = 0; ci < nlive; ++ci) {
-    const int c = chan_at(ci), c1 = chan_at(ci + 1), c2 = chan_at(ci + 2);  // this live channel and the next two
+    const int c = sc0, c1 = sc1, c2 = sc2;  // this live channel and the next two
 #ifdef SPR_STAMPS
     unsigned long long st[kStampPoints] = {};
 #endif
@@ -294,20 +320,29 @@ pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_by
         z[2 * mm] = cmul(cmake(a.x, a.y), cmake(b.x, b.y));
         z[2 * mm + 1] = cmul(cmake(a.z, a.w), cmake(b.z, b.w));
       }
-      if (rc == 0 && tid < 16) {  // image column 0: pack column nw/2 into its imaginary part
-        const cf* nq = nyq + (ci & 1) * NT;
+    };
+    // image column 0 (the first 16 lanes of wave 0) packs column nw/2 into its imaginary part: the product of the two
+    // sides' Nyquist values was stored by the row pass two channels ago
+    auto add_nyq = [&](cf (&z)[12]) {
+      if (tid < 16) {
+        const cf* nq = nyq + (ci & 1) * S::kNyqBuf + tc;
+        cf pr[12];
 #pragma unroll
-        for (int m = 0; m < 12; ++m) {
-          const int k1 = tc + 16 * m;
-          z[m] = pk_add_i(z[m], cmul(nq[k1], nq[C::NH + k1]));
-        }
+        for (int m = 0; m < 12; ++m) pr[m] = nq[16 * m];
+#pragma unroll
+        for (int m = 0; m < 12; ++m) z[m] = pk_add_i(z[m], pr[m]);
       }
     };
     // ... -> 12-point stage -> twiddles
     auto stage12 = [&](cf (&z)[12]) {
-      pfa12<+1>(z);
+      cf w[12];  // the eleven twiddle reads fly during the 48 packed instructions of the 12-point stage
 #pragma unroll
-      for (int p = 1; p < 12; ++p) z[p] = cmul(z[p], twt_h[p * 16 + tc]);
+      for (int p = 1; p < 12; ++p) w[p] = twt_h[p * 16 + tc];
+      sched_fence();
+      pfa12<+1>(z);
+      sched_fence();
+#pragma unroll
+      for (int p = 1; p < 12; ++p) z[p] = cmul(z[p], w[p]);
     };
     // exchange: row p of the wave's image holds U[p] of all 64 lanes.  Rows 0..5 in the wave's buffer, rows 6..11 in the
     // image columns of this unit (written at its end, dead until then); `skew` makes row 6 continue the bank sequence of
@@ -352,6 +387,8 @@ pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_by
       issue_nyq(c2);
       product(za, 0);
       issue_unit(c, 1);  // unit B's operands fly during the 12-point stage of A and the wait
+      sched_fence();  // (wave 0's LDS round trip below starts after the loads, not before them)
+      add_nyq(za);
       stage12(za);
 #pragma unroll
       for (int p = 0; p < 12; ++p) pin(za[p]);  // (or the compiler sinks the arithmetic below the wait)
@@ -408,10 +445,12 @@ pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_by
         }
       }
       SPR_STAMP(8);
+      const int list_next = chan_at(ci + 3);  // (one LDS read among the image reads' returns)
       if (SPR_ABL != 4) Dft<16, +1>::run(z);
       sched_fence();
       // the 1/sigma slice is needed at the very end: requested only now, it does not sit in registers during the
-      // 16-point stage (the exchange below is what hides its latency)
+      // 16-point stage (the exchange below is what hides its latency; three of the six loads requested before that
+      // stage measured 2 % slower)
       float4 iv[6];
       const unsigned so_inv = inv_base + static_cast<unsigned>(c) * static_cast<unsigned>(g.inv_per_chan) * 4u;
 #pragma unroll
@@ -451,7 +490,7 @@ pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_by
         const cf ia = cmake(iv[pp].x, iv[pp].y), ib = cmake(iv[pp].z, iv[pp].w);
         acc[pp][0] = oa * ia + acc[pp][0];
         acc[pp][1] = ob * ib + acc[pp][1];
-        if (maps_out && half == 0) {  // debug / parity output of the per-channel maps (spr_ncc_maps): one uniform branch
+        if (MAPS && half == 0) {  // parity output of the per-channel maps (spr_ncc_maps): its own instantiation
           const int n1 = t3 + 3 * pp;
           const int real_row = wv * C::kRowGroups + grp;
           if (n1 < 16 && grp < C::kRowGroups && real_row < g.ih) {
@@ -464,7 +503,10 @@ pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_by
           }
         }
       }
-      nyq[(ci & 1) * NT + tid] = tid < C::NH ? nyq_g : nyq_q;  // the live channel after next's
+      store_nyq(ci & 1, tid);  // the live channel after next's
+      sc0 = sc1;
+      sc1 = sc2;
+      sc2 = uniform(list_next);
     }
     SPR_STAMP(10);
 #ifdef SPR_STAMPS
@@ -547,7 +589,7 @@ size_t pair6_lds_bytes() { return Six<C6>::kLdsBytes; }
 int pair6_max_rows() { return C6::kRows6; }
 int pair6_max_cols() { return 64; }  // outputs x[2m], x[2m+1] for m < 32
 
-template <bool PEAKS>
+template <bool PEAKS, bool MAPS>
 static int launch_pair6_t(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
   if (!s.six_ctab) { set_error("pair6_kernel: the plan has no pre-twist table"); return SPR_ERR_ARG; }
   using S = Six<C6>;
@@ -561,14 +603,14 @@ static int launch_pair6_t(const NccGeom& g, const PlanScratch& s, const PairCall
   const size_t lds_bytes = S::kLdsBytes + 2 * sizeof(unsigned short) * static_cast<size_t>(g.channels);
   a.prio_mode = env_int("SPR_P6_PRIO", 2);
   const int64_t tiles = static_cast<int64_t>(ceil_div(static_cast<int>(c.nq), kTileQ6)) * a.tiles_g;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pair6_kernel<C6, PEAKS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pair6_kernel<C6, PEAKS, MAPS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             kLdsLimit);
   // HIP refuses grids of 2^32 work-items and more: launch in slices of pair tiles
   const int64_t max_tiles = pair_tiles_per_launch(kTileQ6 * kTileG6 / 2, 2 * C6::NT);
   for (int64_t t0 = 0; t0 < tiles; t0 += max_tiles) {
     const int64_t n = tiles - t0 < max_tiles ? tiles - t0 : max_tiles;
     a.tile0 = static_cast<int>(t0);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair6_kernel<C6, PEAKS>), dim3(static_cast<unsigned>(n * (kTileQ6 * kTileG6 / 2))), dim3(2 * C6::NT),
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair6_kernel<C6, PEAKS, MAPS>), dim3(static_cast<unsigned>(n * (kTileQ6 * kTileG6 / 2))), dim3(2 * C6::NT),
                        lds_bytes, c.stream, a, static_cast<const unsigned char*>(c.pq),
                        prepared_query_item_bytes(g, SPR_NCC_FFT), static_cast<const unsigned char*>(c.pg),
                        prepared_gallery_item_bytes(g, SPR_NCC_FFT), c.scores, static_cast<long long>(c.ld),
@@ -581,7 +623,8 @@ static int launch_pair6_t(const NccGeom& g, const PlanScratch& s, const PairCall
 
 int launch_pair6(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
   if (c.nq == 0 || c.ng == 0) return SPR_OK;
-  return c.peak_yx ? launch_pair6_t<true>(g, s, c) : launch_pair6_t<false>(g, s, c);
+  if (c.peak_yx) return launch_pair6_t<true, false>(g, s, c);
+  return c.maps_out ? launch_pair6_t<false, true>(g, s, c) : launch_pair6_t<false, false>(g, s, c);
 }
 
 }  // namespace spr
