@@ -26,12 +26,14 @@
  *  - Feature maps are dense row-major [item][channel][row][col] ("[N,C,h,w]"),
  *    float32 unless the plan's dtype says otherwise (customtypes.py:7-14,
  *    network.py:241).
- *  - Thread safety: a plan may be used from one host thread at a time; different
- *    plans are independent.
- *  - A plan may own device scratch its kernels write (the workspace of the 384 x 192 grid, the counters of the team
- *    schedule, the correction matrix of SPR_NCC_MFMA).  Such a plan orders its own calls: spr_ncc_score / spr_ncc_maps record
- *    an event behind their launches and a call arriving on another stream waits for it, so two streams sharing a plan
- *    serialise on it instead of racing; use one plan per stream to overlap layers.
+ *  - Thread safety: an spr_ncc_plan may be used from several host threads and streams at once (its preparing and scoring
+ *    calls; create, enable_peaks and destroy are the owner's).  Every other kind of plan: one host thread at a time.
+ *    Different plans are independent.
+ *  - An spr_ncc_plan may own device scratch its kernels write: the workspace of the 384 x 192 grid (preparation and
+ *    scoring) or the correction matrix of SPR_NCC_MFMA (scoring).  Calls that touch it serialise on the plan: host threads
+ *    take turns, and a call arriving on another stream than the last waits for an event recorded behind that one's
+ *    launches.  Plans that own nothing (LDS-resident FFT plans, direct plans) pay no lock and no event.  Use one plan per
+ *    stream to overlap equal-shaped layers.
  *  - spr_*_plan_create / spr_*_plan_destroy are synchronous (hipMalloc / hipMemcpy / hipFree on the current device): create
  *    plans outside the hot path, with the device that will run them current.
  */

@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <initializer_list>
+#include <mutex>
 #include <new>
 #include <vector>
 
@@ -33,8 +34,6 @@ int env_int(const char* name, int fallback) {
   const char* v = std::getenv(name);
   return v && *v ? std::atoi(v) : fallback;
 }
-
-bool team_schedule() { return env_int("SPR_NCC_TEAM", 0) == 1; }
 
 int64_t pair_tiles_per_launch(int pairs_per_tile, int threads) {
   int64_t t = ((static_cast<int64_t>(1) << 32) - 1) / (static_cast<int64_t>(pairs_per_tile) * threads);
@@ -72,35 +71,48 @@ struct spr_ncc_plan {
   int method;              // resolved: SPR_NCC_FFT, SPR_NCC_DIRECT, SPR_NCC_MFMA or SPR_NCC_MFMA_F32
   spr::PlanScratch scratch{};
   bool mfma_peaks = false;  // matrix-core plans: spr_ncc_plan_enable_peaks was called (their peak form is opt-in)
-  // A plan that owns device scratch its kernels write (mfma_x, team_sync, ws) orders its own calls: every scoring call
-  // records `done` behind its launches, and a call that arrives on ANOTHER stream waits for it first - two streams sharing a
-  // plan (one scorer, equal-shaped layers on separate streams) then serialise instead of racing on the scratch.
-  hipEvent_t done = nullptr;
+  // A plan that owns device scratch its kernels write (the FFT workspace `ws`, the correction matrix `mfma_x`) orders the
+  // calls that touch it (PlanCall below); what a plan owns is known when it is created.
+  bool owns_scratch = false;
+  std::mutex mutex;         // held by the one call that is enqueueing work on the scratch
+  hipEvent_t done = nullptr;  // recorded behind that call's launches
   hipStream_t last_stream = nullptr;
   bool used = false;
-  // (the counters are written only by the team schedule: the same test as the launcher's, pair_t in ncc_fft_kernels.h)
-  bool owns_scratch() const { return scratch.mfma_x || scratch.ws || (scratch.team_sync && spr::team_schedule()); }
 };
 
-// before / after the launches of a scoring call on stream s
-static int plan_enter(spr_ncc_plan* plan, hipStream_t s) {
-  if (!plan->owns_scratch()) return SPR_OK;
-  if (!plan->done && hipEventCreateWithFlags(&plan->done, hipEventDisableTiming) != hipSuccess) {
-    spr::set_error("hipEventCreate failed");
-    return SPR_ERR_HIP;
+// One call that touches scratch the plan owns, on stream s: host threads take turns, and a call that arrives on ANOTHER
+// stream than the last one first waits for that one's launches - two streams sharing a plan (one scorer, equal-shaped layers
+// on separate streams) then serialise instead of racing on the scratch.  Nothing at all on a plan that owns none.
+class PlanCall {
+ public:
+  PlanCall(spr_ncc_plan* plan, hipStream_t s) : plan_(plan->owns_scratch ? plan : nullptr), stream_(s) {
+    if (!plan_) return;
+    plan_->mutex.lock();
+    if (!plan_->done && hipEventCreateWithFlags(&plan_->done, hipEventDisableTiming) != hipSuccess) {
+      spr::set_error("hipEventCreate failed");
+      rc = SPR_ERR_HIP;
+    } else if (plan_->used && plan_->last_stream != s && hipStreamWaitEvent(s, plan_->done, 0) != hipSuccess) {
+      spr::set_error("hipStreamWaitEvent failed");
+      rc = SPR_ERR_HIP;
+    }
   }
-  if (plan->used && plan->last_stream != s && hipStreamWaitEvent(s, plan->done, 0) != hipSuccess) {
-    spr::set_error("hipStreamWaitEvent failed");
-    return SPR_ERR_HIP;
+  ~PlanCall() {
+    if (!plan_) return;
+    if (rc == SPR_OK) {
+      (void)hipEventRecord(plan_->done, stream_);
+      plan_->last_stream = stream_;
+      plan_->used = true;
+    }
+    plan_->mutex.unlock();
   }
-  return SPR_OK;
-}
-static void plan_leave(spr_ncc_plan* plan, hipStream_t s) {
-  if (!plan->owns_scratch() || !plan->done) return;
-  (void)hipEventRecord(plan->done, s);
-  plan->last_stream = s;
-  plan->used = true;
-}
+  PlanCall(const PlanCall&) = delete;
+  PlanCall& operator=(const PlanCall&) = delete;
+  int rc = SPR_OK;  // not SPR_OK: launch nothing
+
+ private:
+  spr_ncc_plan* plan_;
+  hipStream_t stream_;
+};
 
 using namespace spr;
 
@@ -201,10 +213,6 @@ extern "C" int spr_ncc_plan_create(const spr_ncc_shape* shape, spr_ncc_plan** pl
   if (method == SPR_NCC_FFT) {
     int rc = make_twiddles(p->geom.nh, &sc.tw_h);
     if (rc == SPR_OK) rc = make_twiddles(p->geom.nw, &sc.tw_w);
-    if (rc == SPR_OK && hipMalloc(reinterpret_cast<void**>(&sc.team_sync), sizeof(unsigned) * 8 * 32) != hipSuccess) {
-      set_error("hipMalloc(team counters) failed");
-      rc = SPR_ERR_HIP;
-    }
     const size_t ws_bytes = fft_workspace_bytes(p->geom);
     if (rc == SPR_OK && ws_bytes > 0) {
       if (hipMalloc(&sc.ws, ws_bytes) != hipSuccess) {
@@ -230,6 +238,7 @@ extern "C" int spr_ncc_plan_create(const spr_ncc_shape* shape, spr_ncc_plan** pl
     }
     if (rc != SPR_OK) { spr_ncc_plan_destroy(p); return rc; }
   }
+  p->owns_scratch = sc.mfma_x || sc.ws;
   *plan_out = p;
   return SPR_OK;
 }
@@ -237,7 +246,7 @@ extern "C" int spr_ncc_plan_create(const spr_ncc_shape* shape, spr_ncc_plan** pl
 extern "C" void spr_ncc_plan_destroy(spr_ncc_plan* plan) {
   if (!plan) return;
   const PlanScratch& sc = plan->scratch;
-  for (void* dev : std::initializer_list<void*>{sc.tw_h, sc.tw_w, sc.team_sync, sc.ws, sc.six_ctab, sc.mfma_x})
+  for (void* dev : std::initializer_list<void*>{sc.tw_h, sc.tw_w, sc.ws, sc.six_ctab, sc.mfma_x})
     if (dev) (void)hipFree(dev);
   if (plan->done) (void)hipEventDestroy(plan->done);
   delete plan;
@@ -268,7 +277,11 @@ static int prepare(spr_ncc_plan* plan, bool is_query, const void* maps, int64_t 
   if (n == 0) return SPR_OK;
   if (!maps || !prepared) { set_error("%s: null pointer", who); return SPR_ERR_ARG; }
   const PrepCall c{is_query, maps, n, prepared, static_cast<hipStream_t>(stream)};
-  if (plan->method == SPR_NCC_FFT) return launch_prep_fft(plan->geom, plan->scratch, c);
+  if (plan->method == SPR_NCC_FFT) {
+    PlanCall guard(plan, c.stream);  // the workspace-mode prep kernels write scratch.ws (an LDS-resident plan owns nothing)
+    return guard.rc != SPR_OK ? guard.rc : launch_prep_fft(plan->geom, plan->scratch, c);
+  }
+  // (matrix-core preparation does not touch the correction matrix: no guard)
   if (plan->method == SPR_NCC_MFMA || plan->method == SPR_NCC_MFMA_F32) return launch_prep_mfma(plan->geom, plan->scratch, c);
   return launch_prep_direct(plan->geom, plan->scratch, c);
 }
@@ -282,18 +295,13 @@ extern "C" int spr_ncc_prepare_gallery(spr_ncc_plan* plan, const void* maps, int
   return prepare(plan, false, maps, n, prepared, stream, "spr_ncc_prepare_gallery");
 }
 
-// the launches of one scoring call, between plan_enter and plan_leave
+// the launches of one scoring call
 static int score_pairs(spr_ncc_plan* plan, const PairCall& c) {
-  int rc = plan_enter(plan, c.stream);
-  if (rc != SPR_OK) return rc;
-  if (plan->method == SPR_NCC_FFT)
-    rc = launch_pair_fft(plan->geom, plan->scratch, c);
-  else if (plan->method == SPR_NCC_MFMA || plan->method == SPR_NCC_MFMA_F32)
-    rc = launch_pair_mfma(plan->geom, plan->scratch, c);
-  else
-    rc = launch_pair_direct(plan->geom, plan->scratch, c);
-  plan_leave(plan, c.stream);
-  return rc;
+  PlanCall guard(plan, c.stream);
+  if (guard.rc != SPR_OK) return guard.rc;
+  if (plan->method == SPR_NCC_FFT) return launch_pair_fft(plan->geom, plan->scratch, c);
+  if (plan->method == SPR_NCC_MFMA || plan->method == SPR_NCC_MFMA_F32) return launch_pair_mfma(plan->geom, plan->scratch, c);
+  return launch_pair_direct(plan->geom, plan->scratch, c);
 }
 
 extern "C" int spr_ncc_score(spr_ncc_plan* plan, const void* pq, int64_t nq, const void* pg, int64_t ng, float* scores,

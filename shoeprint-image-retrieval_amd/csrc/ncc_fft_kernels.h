@@ -300,22 +300,21 @@ struct PairArgs {
   int inv_per_chan;  // floats of 1/sigma per channel
   int accumulate;
   int tile0;         // tile mode: first 16 x 16 pair tile of this launch (launches are sliced: HIP's grid limit)
-  // team mode (team_size > 0): persistent grid of 8 teams (one per XCD) x team_size resident workgroups
+  // workspace mode (team_size > 0): persistent grid of 8 teams (one per XCD) x team_size resident workgroups
   int team_size;     // workgroups per team = pairs per epoch
   int strip_q;       // queries per strip (the last strip may hold fewer)
   int strips;        // number of query strips
   int epochs_full;   // epochs of a full strip = ceil(strip_q * ng / team_size)
   int epochs_total;  // over all strips
-  int sync_polls;    // bound of the soft team barrier
-  int sync_every;    // channels between mid-pair team barriers (0: only at the start of a pair)
+  int kernarg_pad[2];  // unused: the arguments behind this struct stay at the offsets the general 192 x 96 instance was tuned
+                       // at (8 bytes earlier its scalar loads regroup and one more SGPR spills)
 };
 
 // RK = rows of a column transform's output kept in the LDS image (compile-time for the tuned variant: the
 // stage-2 outputs beyond it are dead code and the stores need no per-row test; 0 = runtime r_rows)
 // BIG: the intermediate image does not fit LDS; it lives in this workgroup's slot of a global workspace (the
-// launch is then always the persistent team grid, one slot per resident workgroup).
-// TEAM: the persistent-grid schedule is its own instantiation, so the default one-pair-per-workgroup kernel
-// carries none of its scalar state (measured: 1.8 % when both lived in one kernel).  BIG implies TEAM.
+// launch is then the persistent grid, one slot per resident workgroup; the default one-pair-per-workgroup kernel
+// carries none of that walk's scalar state).
 // PEAKS: the form behind spr_ncc_score_peaks - the arg-max beside the max, in the epilogue only - is its own instantiation
 // (as a runtime branch it cost the plain form registers, spills and occupancy in most instances).  A translation unit
 // instantiates one form: ncc_fft_peaks.hip defines SPR_FFT_PEAKS_TU before it includes this file.
@@ -324,13 +323,13 @@ constexpr bool kPeaksTu = true;
 #else
 constexpr bool kPeaksTu = false;
 #endif
-template <class C, int RR, int KW, int PF, int RK, bool BIG, bool TEAM, bool PEAKS>
+template <class C, int RR, int KW, int PF, int RK, bool BIG, bool PEAKS>
 __global__ void __launch_bounds__(C::NT, BIG ? 1 : ((C::NT == 64 && RK > 0) ? 4 : 2))
 pair_fft_kernel(PairArgs g, const unsigned char* __restrict__ pq, size_t q_item_bytes,
                 const unsigned char* __restrict__ pg, size_t g_item_bytes, float* __restrict__ scores,
                 long long ld, long long col0, float* __restrict__ maps_out,
                 const cf* __restrict__ tw_h, const cf* __restrict__ tw_w, unsigned r_off, unsigned xbuf_off,
-                unsigned nyq_off_lds, unsigned* __restrict__ team_sync, unsigned char* __restrict__ ws,
+                unsigned nyq_off_lds, unsigned char* __restrict__ ws,
                 size_t slot_bytes, int32_t* __restrict__ peak_yx, int32_t* __restrict__ peak_tag, int32_t tag) {
   using GH = typename C::GH;
   using GW = typename C::GW;
@@ -424,23 +423,18 @@ pair_fft_kernel(PairArgs g, const unsigned char* __restrict__ pq, size_t q_item_
 
   // ---- which pairs ------------------------------------------------------------------------------
   // tile mode: this workgroup's one pair from the 16 x 16 tile mapping above the kernel.
-  // team mode: workgroup = member of team (blockIdx % 8 = XCD); the team walks its share of the epochs, an
+  // workspace mode: workgroup = member of team (blockIdx % 8 = XCD); the team walks its share of the epochs, an
   // epoch being team_size consecutive pairs of a query strip in gallery-major order (so ~strip_q queries x
-  // team_size/strip_q gallery items: every spectrum line has many readers on this L2), and the members
-  // start each pair together (soft barrier) so that those readers are close in time as well.
-  static_assert(TEAM || !BIG, "the workspace mode runs on the persistent grid");
+  // team_size/strip_q gallery items: every spectrum line has many readers on this L2).
   const int team = static_cast<int>(blockIdx.x) & 7, member = static_cast<int>(blockIdx.x) >> 3;
-  unsigned* sync_ctr = team_sync + team * 32;
-  unsigned sync_target = 0;
-  int epoch = 0, epoch_end = 1, syncs_per_pair = 1;
-  if constexpr (TEAM) {
-    syncs_per_pair = g.sync_every > 0 ? ceil_div(g.channels, g.sync_every) : 1;
+  int epoch = 0, epoch_end = 1;
+  if constexpr (BIG) {
     epoch = static_cast<int>(static_cast<long long>(g.epochs_total) * team / 8);
     epoch_end = static_cast<int>(static_cast<long long>(g.epochs_total) * (team + 1) / 8);
   }
   for (; epoch < epoch_end; ++epoch) {
   int qi, gi_item;
-  if constexpr (TEAM) {
+  if constexpr (BIG) {
     int strip = epoch / g.epochs_full;
     strip = strip < g.strips ? strip : g.strips - 1;
     const int q0 = strip * g.strip_q;
@@ -448,17 +442,8 @@ pair_fft_kernel(PairArgs g, const unsigned char* __restrict__ pq, size_t q_item_
     const long long p = static_cast<long long>(epoch - strip * g.epochs_full) * g.team_size + member;
     gi_item = static_cast<int>(p / qn);
     qi = q0 + static_cast<int>(p - static_cast<long long>(gi_item) * qn);
-    if (gi_item >= ng) {  // ragged last epoch of a strip: keep the team's count whole and move on
-      if (tid == 0) team_arrive(sync_ctr, static_cast<unsigned>(syncs_per_pair));
-      sync_target += static_cast<unsigned>(syncs_per_pair) * g.team_size;
-      continue;
-    }
-    sync_target += g.team_size;
-    if (tid == 0) {
-      team_arrive(sync_ctr, 1u);
-      team_wait(sync_ctr, sync_target, g.sync_polls);
-    }
-    __syncthreads();
+    if (gi_item >= ng) continue;  // ragged last epoch of a strip
+    __syncthreads();  // the previous pair's epilogue (red, the LDS tables) is behind every wave before this pair's stores
   } else {
     const int tiles_g = ceil_div(ng, kTileG);
     const int tile = g.tile0 + static_cast<int>(blockIdx.x) / (kTileQ * kTileG);
@@ -492,13 +477,6 @@ pair_fft_kernel(PairArgs g, const unsigned char* __restrict__ pq, size_t q_item_
   __syncthreads();
 
   for (int c = 0; c < g.channels; ++c) {
-    if (TEAM && g.sync_every > 0 && c > 0 && c % g.sync_every == 0) {
-      sync_target += g.team_size;
-      if (tid == 0) {  // the other waves run on to the next workgroup barrier
-        team_arrive(sync_ctr, 1u);
-        team_wait(sync_ctr, sync_target, g.sync_polls);
-      }
-    }
     // lane coordinates, re-derived from an opaque copy of the lane id every channel (see spr::opaque)
     const int tidv = opaque(tid0);
     const int gc = tidv / C::TGH, tc = tidv - gc * C::TGH;  // column-pass group / lane in group
@@ -843,80 +821,72 @@ int prep_launch(const NccGeom& g, const PlanScratch& s, const PrepCall& c) {
   return SPR_OK;
 }
 template <class C>
+int no_lds_mode() {
+  set_error("FFT grid %dx%d has workspace-mode kernels only", C::NH, C::NW);
+  return SPR_ERR_UNSUPPORTED;
+}
+template <class C, bool BIG_ONLY>  // BIG_ONLY: see pair_t
 int prep_t(const NccGeom& g, const PlanScratch& s, const PrepCall& c) {
 #ifndef SPR_SAN_SUBSET
   if (g.big) return prep_launch<C, true, kThreads>(g, s, c);
 #endif
-  if (prep_threads<C>(g, c.is_query) == 512) return prep_launch<C, false, 512>(g, s, c);
-  return prep_launch<C, false, kThreads>(g, s, c);
+  if constexpr (BIG_ONLY) return no_lds_mode<C>();
+  else {
+    if (prep_threads<C>(g, c.is_query) == 512) return prep_launch<C, false, 512>(g, s, c);
+    return prep_launch<C, false, kThreads>(g, s, c);
+  }
 }
 
-constexpr int kTeamCounters = 8 * 32;  // one 128-byte line per team
-
-template <class C, int RR, int KW, int PF, int RK, bool BIG, bool TEAM>
+template <class C, int RR, int KW, int PF, int RK, bool BIG>
 int pair_launch(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
   const int64_t nq = c.nq, ng = c.ng;
-  // (spr_ncc_maps on an LDS-resident plan has never handed the kernel the counters; its tile schedule does not read them)
-  unsigned* team_sync = c.maps_out && !BIG ? nullptr : s.team_sync;
   const PairFftLds l = pair_fft_lds<C>(g);
   const int64_t tiles = static_cast<int64_t>(ceil_div(static_cast<int>(nq), kTileQ)) * ceil_div(static_cast<int>(ng), kTileG);
   PairArgs a{};
   a.channels = g.channels; a.nq = static_cast<int>(nq); a.ng = static_cast<int>(ng);
   a.ih = g.ih; a.iw = g.iw; a.r_rows = g.r_rows; a.r_stride = g.r_stride; a.rounds_r = g.rounds_r;
   a.inv_per_chan = g.inv_per_chan; a.accumulate = c.accumulate;
-  const void* kernel = reinterpret_cast<const void*>(pair_fft_kernel<C, RR, KW, PF, RK, BIG, TEAM, kPeaksTu>);
+  const void* kernel = reinterpret_cast<const void*>(pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu>);
   (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
   unsigned grid = 0;
-  // ---- team mode: a persistent grid that exactly fills the device, 8 teams of co-resident workgroups ----
+  // ---- workspace mode: a persistent grid that exactly fills the device, 8 teams of co-resident workgroups, one
+  // workspace slot per resident workgroup (the only launch form of this mode) ----
   int per_cu = 0, cus = 0, dev = 0;
-  if (TEAM && !team_sync) { set_error("pair_fft_kernel: the team schedule needs the plan's counters"); return SPR_ERR_ARG; }
-  if (TEAM && hipGetDevice(&dev) == hipSuccess &&
+  if (BIG && hipGetDevice(&dev) == hipSuccess &&
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pair_fft_kernel<C, RR, KW, PF, RK, BIG, TEAM, kPeaksTu>, C::NT, l.total) == hipSuccess &&
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu>, C::NT, l.total) == hipSuccess &&
       per_cu > 0 && cus >= 8) {
     int team_size = cus / 8 * per_cu;
-    if (BIG) {  // one workspace slot per resident workgroup: the persistent grid is the only launch form
-      const size_t slots = s.ws ? s.ws_bytes / l.slot_bytes : 0;
-      if (slots < 8) { set_error("pair_fft_kernel: workspace too small"); return SPR_ERR_WORKSPACE; }
-      if (static_cast<size_t>(team_size) * 8 > slots) team_size = static_cast<int>(slots / 8);
-    }
-    {
-      const int strip_max = env_int("SPR_NCC_STRIP_Q", 16) > 0 ? env_int("SPR_NCC_STRIP_Q", 16) : 16;
-      const int strips = ceil_div(static_cast<int>(nq), strip_max);
-      a.team_size = team_size;
-      a.strips = strips;
-      a.strip_q = ceil_div(static_cast<int>(nq), strips);
-      a.strips = ceil_div(static_cast<int>(nq), a.strip_q);
-      a.epochs_full = static_cast<int>((static_cast<int64_t>(a.strip_q) * ng + team_size - 1) / team_size);
-      const int q_last = static_cast<int>(nq) - (a.strips - 1) * a.strip_q;
-      a.epochs_total = (a.strips - 1) * a.epochs_full + static_cast<int>((static_cast<int64_t>(q_last) * ng + team_size - 1) / team_size);
-      a.sync_polls = env_int("SPR_NCC_TEAM_POLLS", BIG ? 0 : 256);
-      a.sync_every = env_int("SPR_NCC_TEAM_EVERY", BIG ? 0 : 32);
-      if (a.sync_every < 0) a.sync_every = 0;
-      grid = 8u * static_cast<unsigned>(team_size);
-      if (hipMemsetAsync(team_sync, 0, sizeof(unsigned) * kTeamCounters, c.stream) != hipSuccess) {
-        set_error("hipMemsetAsync(team counters) failed");
-        return SPR_ERR_HIP;
-      }
-    }
+    const size_t slots = s.ws ? s.ws_bytes / l.slot_bytes : 0;
+    if (slots < 8) { set_error("pair_fft_kernel: workspace too small"); return SPR_ERR_WORKSPACE; }
+    if (static_cast<size_t>(team_size) * 8 > slots) team_size = static_cast<int>(slots / 8);
+    const int strip_max = env_int("SPR_NCC_STRIP_Q", 16) > 0 ? env_int("SPR_NCC_STRIP_Q", 16) : 16;
+    const int strips = ceil_div(static_cast<int>(nq), strip_max);
+    a.team_size = team_size;
+    a.strip_q = ceil_div(static_cast<int>(nq), strips);
+    a.strips = ceil_div(static_cast<int>(nq), a.strip_q);
+    a.epochs_full = static_cast<int>((static_cast<int64_t>(a.strip_q) * ng + team_size - 1) / team_size);
+    const int q_last = static_cast<int>(nq) - (a.strips - 1) * a.strip_q;
+    a.epochs_total = (a.strips - 1) * a.epochs_full + static_cast<int>((static_cast<int64_t>(q_last) * ng + team_size - 1) / team_size);
+    grid = 8u * static_cast<unsigned>(team_size);
   }
-  if (TEAM && a.team_size == 0) { set_error("pair_fft_kernel: could not size the persistent grid"); return SPR_ERR_HIP; }
+  if (BIG && a.team_size == 0) { set_error("pair_fft_kernel: could not size the persistent grid"); return SPR_ERR_HIP; }
   // tile mode: HIP refuses grids of 2^32 work-items and more (65 536 tiles of 256-lane workgroups, e.g. 256 queries
   // against a 65 535-item gallery chunk of small maps), so a launch takes a slice of the tiles
-  const int64_t max_tiles = TEAM ? tiles : pair_tiles_per_launch(kTileQ * kTileG, C::NT);
-  for (int64_t t0 = 0; t0 < (TEAM ? 1 : tiles); t0 += max_tiles) {
-    if (!TEAM) {
+  const int64_t max_tiles = BIG ? tiles : pair_tiles_per_launch(kTileQ * kTileG, C::NT);
+  for (int64_t t0 = 0; t0 < (BIG ? 1 : tiles); t0 += max_tiles) {
+    if (!BIG) {
       const int64_t n = tiles - t0 < max_tiles ? tiles - t0 : max_tiles;
       a.tile0 = static_cast<int>(t0);
       grid = static_cast<unsigned>(n * kTileQ * kTileG);
     }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_fft_kernel<C, RR, KW, PF, RK, BIG, TEAM, kPeaksTu>), dim3(grid),
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu>), dim3(grid),
                        dim3(C::NT), l.total, c.stream, a, static_cast<const unsigned char*>(c.pq),
                        prepared_query_item_bytes(g, SPR_NCC_FFT), static_cast<const unsigned char*>(c.pg),
                        prepared_gallery_item_bytes(g, SPR_NCC_FFT), c.scores,
                        static_cast<long long>(c.ld), static_cast<long long>(c.col0), c.maps_out, s.tw_h, s.tw_w,
                        static_cast<unsigned>(l.r_off), static_cast<unsigned>(l.xbuf_off),
-                       static_cast<unsigned>(l.nyq_off), team_sync, static_cast<unsigned char*>(s.ws), l.slot_bytes,
+                       static_cast<unsigned>(l.nyq_off), static_cast<unsigned char*>(s.ws), l.slot_bytes,
                        c.peak_yx, c.peak_tag, c.tag);
     const int rc = check_launch("pair_fft_kernel");
     if (rc != SPR_OK) return rc;
@@ -930,28 +900,29 @@ int pair_launch(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
 // variant 11 x 4 (up to 256 x 128), general variant for the rest.
 constexpr int kBigMidKw = 11, kBigMidRr = 4;
 // tuned variant: KW_A x RR_A with PFA prefetch buffers; general variant: everything kept, one buffer
-template <class C, int PFA, bool BIG, bool TEAM>
+template <class C, int PFA, bool BIG>
 int pair_tb(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
-  if (g.tight) return pair_launch<C, C::RR_A, C::KW_A, PFA, rk_tuned<C>(), BIG, TEAM>(g, s, c);
+  if (g.tight) return pair_launch<C, C::RR_A, C::KW_A, PFA, rk_tuned<C>(), BIG>(g, s, c);
   if constexpr (BIG) {  // the workspace instance's middle variant (fill_geometry): the widest map of its grid, 4 row rounds
-    if (g.keep_w == kBigMidKw) return pair_launch<C, kBigMidRr, kBigMidKw, 1, 0, BIG, TEAM>(g, s, c);
+    if (g.keep_w == kBigMidKw) return pair_launch<C, kBigMidRr, kBigMidKw, 1, 0, BIG>(g, s, c);
   }
-  return pair_launch<C, C::RR_B, C::KW_B, 1, 0, BIG, TEAM>(g, s, c);
+  return pair_launch<C, C::RR_B, C::KW_B, 1, 0, BIG>(g, s, c);
 }
-template <class C, int PFA>
+// BIG_ONLY: a grid that fft_geometry never selects in LDS mode has no LDS-mode instances
+template <class C, int PFA, bool BIG_ONLY>
 int pair_t(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
-#ifndef SPR_SAN_SUBSET  // (the sanitizer build of the CPU emulation compiles the default schedule only)
-  if (g.big) return pair_tb<C, PFA, true, true>(g, s, c);
-  if (s.team_sync && !c.maps_out && team_schedule()) return pair_tb<C, PFA, false, true>(g, s, c);
+#ifndef SPR_SAN_SUBSET  // (the sanitizer build of the CPU emulation compiles the LDS-mode kernels only)
+  if (g.big) return pair_tb<C, PFA, true>(g, s, c);
 #endif
-  return pair_tb<C, PFA, false, false>(g, s, c);
+  if constexpr (BIG_ONLY) return no_lds_mode<C>();
+  else return pair_tb<C, PFA, false>(g, s, c);
 }
 
 using PrepFn = int (*)(const NccGeom&, const PlanScratch&, const PrepCall&);
-template <class C>
+template <class C, bool BIG_ONLY>
 constexpr PrepFn prep_fn() {  // (the peaks translation unit launches pairs only and instantiates no prep kernel)
   if constexpr (kPeaksTu) return nullptr;
-  else return &prep_t<C>;
+  else return &prep_t<C, BIG_ONLY>;
 }
 
 template <class C, int PFA, bool BIG_ONLY = false>
@@ -959,7 +930,7 @@ constexpr FftEntry entry() {
   return FftEntry{C::NH,   C::NW,   C::EH,   C::TGH,  C::EW,   C::TGW, C::NT, C::GW::SPL,
                   C::KW_A, C::RR_A, C::KW_B, C::RR_B, rk_tuned<C>(),
                   (C::NH & (C::NH - 1)) == 0 && (C::NW & (C::NW - 1)) == 0,
-                  C::kSpecPerChan, prep_lds_total_t<C>, pair_lds_total_t<C>, prep_fn<C>(), pair_t<C, PFA>,
+                  C::kSpecPerChan, prep_lds_total_t<C>, pair_lds_total_t<C>, prep_fn<C, BIG_ONLY>(), pair_t<C, PFA, BIG_ONLY>,
                   prep_slot_bytes_t<C>, pair_slot_bytes_t<C>, BIG_ONLY, false};
 }
 
@@ -969,7 +940,7 @@ size_t no_slot_bytes(const NccGeom&) { return 0; }
 template <class C>
 constexpr FftEntry entry6() {
   return FftEntry{C::NH, C::NW, C::EH, C::TGH, C::EW, C::TGW, C::NT, C::GW::SPL, 0, 0, 0, 0, 0, false,
-                  C::kSpecPerChan, prep_lds_total_t<C>, pair6_lds_total, prep_fn<C>(), launch_pair6,
+                  C::kSpecPerChan, prep_lds_total_t<C>, pair6_lds_total, prep_fn<C, false>(), launch_pair6,
                   prep_slot_bytes_t<C>, no_slot_bytes, false, true};
 }
 

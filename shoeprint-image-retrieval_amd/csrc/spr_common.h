@@ -87,7 +87,6 @@ struct PrepCall {
 };
 struct PlanScratch {      // null where the plan's method has none
   cf* tw_h; cf* tw_w;     // FFT: exp(-2*pi*i*k/nh), k < nh, and the same for nw
-  unsigned* team_sync;    // FFT: 8 x 32 arrival counters of the pair kernel's workgroup teams
   void* ws; size_t ws_bytes;  // FFT "big" geometries (maps beyond LDS): the working set
   float* six_ctab;        // six-wave pair kernel: its pre-twist table (nw/2 floats)
   float* mfma_x;          // matrix-core method, exact form: correction matrix (one call at a time per plan)
@@ -96,7 +95,6 @@ struct PlanScratch {      // null where the plan's method has none
 // The scorer's environment switches are all read through env_int: the method switches when a
 // plan is created (the *_geometry functions), the others at every launch.
 int env_int(const char* name, int fallback);  // the variable as an integer; `fallback` if unset or empty
-bool team_schedule();                          // SPR_NCC_TEAM=1: LDS-resident FFT plans score on the persistent team grid
 
 // Launchers (each method in its own .hip file).  All enqueue on the call's stream and return SPR_OK or an error code.
 int launch_prep_direct(const NccGeom& g, const PlanScratch& s, const PrepCall& c);

@@ -52,21 +52,6 @@ __device__ __forceinline__ void sched_group() { __builtin_amdgcn_sched_group_bar
 // Pin a value in its vector registers at this point of the program (the compiler may not move its computation below).
 __device__ __forceinline__ void pin(f32x2& v) { asm volatile("" : "+v"(v)); }
 
-// ---- soft team barrier (locality hint, never a correctness dependency) ------------------------------
-// Workgroups that share an L2 announce themselves on a monotonic counter and wait, for a BOUNDED number of
-// polls, until the whole team has arrived.  A team member that is late (or not resident at all) only costs
-// the others the timeout: every wave leaves the wait, and results never depend on it.
-__device__ __forceinline__ void team_arrive(unsigned* counter, unsigned n) {
-  __hip_atomic_fetch_add(counter, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void team_wait(unsigned* counter, unsigned target, int max_polls) {
-  for (int i = 0; i < max_polls; ++i) {
-    const unsigned seen = __hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (static_cast<int>(seen - target) >= 0) break;
-    __builtin_amdgcn_s_sleep(16);
-  }
-}
-
 // Streamed operands through buffer loads: a wave-uniform resource descriptor (base + size, four scalar registers),
 // a 32-bit byte offset per lane and a wave-uniform byte offset in a scalar register.  No 64-bit vector address
 // arithmetic per load (three vector instructions each with flat global loads), and the compiler still counts the

@@ -10,7 +10,8 @@
 // This file is plain host C++ (no device code): every operator checks its tensors, takes PyTorch's CURRENT HIP stream and
 // calls the same extern "C" entry points the ctypes binding (_lib.py) calls, so both routes run the same kernels bit for
 // bit.  Scratch (prepared spectra, workspaces) comes from PyTorch's caching allocator on that stream; plans are cached per
-// shape class for the life of the process.  Nothing synchronises.
+// shape class for the life of the process and shared by every PyTorch thread and stream - safely, because the library orders
+// the calls that touch scratch a plan owns (the header's conventions).  Nothing synchronises.
 #include <ATen/ATen.h>
 #include <ATen/hip/HIPContext.h>
 #include <c10/hip/HIPStream.h>

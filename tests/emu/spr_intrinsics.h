@@ -46,10 +46,6 @@ inline void sched_fence() {}
 template <int MASK, int SIZE>
 inline void sched_group() {}
 
-// soft team barrier: workgroups run one after another here, so the wait is the timeout case (returns at once)
-inline void team_arrive(unsigned* counter, unsigned n) { __atomic_fetch_add(counter, n, __ATOMIC_RELAXED); }
-inline void team_wait(unsigned*, unsigned, int) {}
-
 // buffer loads: the hardware's range check (lane offset + access size against the descriptor's size, the uniform
 // offset unchecked) returns zeros; here a violation aborts - the kernels never rely on it
 struct BufRsrc {

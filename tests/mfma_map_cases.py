@@ -62,8 +62,7 @@ from shoeprint_image_retrieval_amd.similarity import _METHODS
 #   C. guard bands, emulation: bands and padding untouched, outputs bit-identical across the fills, scores within 1.6e-6 of the
 #      oracle (mfma_f32; the others 6.4e-7 and below).  MI355X: not measured.
 
-ENV_NAMES = ("SPR_NCC_MFMA_EXACT", "SPR_MFMA_PREP", "SPR_MFMA_F32_MEAN", "SPR_NCC_MAX_TILES", "SPR_NCC_FORCE_BIG", "SPR_NCC_SIX",
-             "SPR_NCC_TEAM")
+ENV_NAMES = ("SPR_NCC_MFMA_EXACT", "SPR_MFMA_PREP", "SPR_MFMA_F32_MEAN", "SPR_NCC_MAX_TILES", "SPR_NCC_FORCE_BIG", "SPR_NCC_SIX")
 
 # form -> (method asked for, storage type, environment while the plan is made)
 FORMS = {

@@ -167,7 +167,7 @@ def _inputs(t, i, channels, dtype):
 
 
 def _set_env(monkeypatch, case):
-    for name in ("SPR_NCC_SIX", "SPR_NCC_FORCE_BIG", "SPR_NCC_TEAM"):
+    for name in ("SPR_NCC_SIX", "SPR_NCC_FORCE_BIG"):
         monkeypatch.delenv(name, raising=False)
     for name, value in case.env:
         monkeypatch.setenv(name, value)
@@ -295,7 +295,6 @@ SWEEP_CASES = [
     SweepCase((9, 7), (126, 64), "192x96/6", 561),
     SweepCase((9, 7), (126, 80), "192x96/4", 609),
     SweepCase((9, 7), (180, 120), "256x128", 891, emu=False),
-    SweepCase((9, 7), (126, 64), "192x96/6", 561, env=(("SPR_NCC_TEAM", "1"),)),
     SweepCase((9, 7), (90, 44), "96x48", 393, env=_BIG),
 ]
 N_TEMPLATES = 3   # an odd query count leaves the second half of the last six-wave workgroup idle

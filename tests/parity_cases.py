@@ -122,23 +122,26 @@ def check_shape_case(scorer, case, tol=TIGHT):
     np.testing.assert_allclose(mat, ref, atol=tol, rtol=0)
 
 
-def check_team_mode(scorer, monkeypatch):
-    """The pair kernel's persistent "team" schedule (opt-in: SPR_NCC_TEAM=1)
-    scores exactly what the one-pair-per-workgroup schedule does: ragged epochs, several query strips."""
+def check_persistent_grid(make_scorer, monkeypatch):
+    """The persistent grid of the workspace-mode pair kernel (SPR_NCC_FORCE_BIG=1 on shapes that also fit LDS) scores exactly
+    what the one-pair-per-workgroup schedule does: ragged epochs, several query strips (SPR_NCC_STRIP_Q=4: 19 queries make
+    five strips)."""
     for nq, ng, case in ((5, 7, (2, 32, 16, 32, 16)), (19, 3, (1, 20, 12, 24, 14)), (1, 9, (2, 32, 16, 32, 16))):
         c, qh, qw, gh, gw = case
         q = [synth.gallery_features(31, 100 + i, c, qh, qw) for i in range(nq)]
         g = [synth.gallery_features(31, i, c, gh, gw) for i in range(ng)]
-        monkeypatch.setenv("SPR_NCC_TEAM", "0")
-        tiles = scorer.score_matrix(q, g)
-        monkeypatch.setenv("SPR_NCC_TEAM", "1")
-        team = scorer.score_matrix(q, g)
-        monkeypatch.setenv("SPR_NCC_TEAM_EVERY", "1")  # a soft barrier every channel as well
-        team_every = scorer.score_matrix(q, g)
-        monkeypatch.delenv("SPR_NCC_TEAM_EVERY")
-        np.testing.assert_array_equal(team, tiles)
-        np.testing.assert_array_equal(team_every, tiles)
-        np.testing.assert_allclose(team, oracle.similarity_matrix(q, g, precise=True), atol=TIGHT, rtol=0)
+        monkeypatch.delenv("SPR_NCC_FORCE_BIG", raising=False)
+        monkeypatch.delenv("SPR_NCC_STRIP_Q", raising=False)
+        tiles = make_scorer().score_matrix(q, g)
+        monkeypatch.setenv("SPR_NCC_FORCE_BIG", "1")
+        grid = make_scorer().score_matrix(q, g)  # a fresh scorer: the mode is fixed when the plan is created
+        monkeypatch.setenv("SPR_NCC_STRIP_Q", "4")
+        strips = make_scorer().score_matrix(q, g)
+        monkeypatch.delenv("SPR_NCC_STRIP_Q")
+        monkeypatch.delenv("SPR_NCC_FORCE_BIG")
+        np.testing.assert_array_equal(grid, tiles)
+        np.testing.assert_array_equal(strips, tiles)
+        np.testing.assert_allclose(grid, oracle.similarity_matrix(q, g, precise=True), atol=TIGHT, rtol=0)
 
 
 def check_config3_bf16_resnet_layer3(scorer, channels):

@@ -71,8 +71,49 @@ def test_golden_conv3_shaped_compare_maps(scorer):
     pc.check_golden_compare_maps(scorer, "conv3")
 
 
-def test_team_schedule(fft_scorer, monkeypatch):
-    pc.check_team_mode(fft_scorer, monkeypatch)
+def test_persistent_grid(lib, monkeypatch):
+    from shoeprint_image_retrieval_amd.similarity import NccScorer
+
+    pc.check_persistent_grid(lambda: NccScorer(method="fft", library=lib), monkeypatch)
+
+
+def test_two_streams_share_a_workspace_plan(lib, monkeypatch):
+    """Two streams on one workspace-mode plan (SPR_NCC_FORCE_BIG=1): each prepares its own gallery and scores it against the
+    same queries, the calls interleaved from the host for 8 rounds.  Preparation and scoring both go through the plan's one
+    workspace, and the library orders such calls, so both matrices equal the single-stream results bit for bit.  A race would
+    show up here only with some probability: the test pins the contract, it does not prove it."""
+    import torch
+    from shoeprint_image_retrieval_amd import synth
+    from shoeprint_image_retrieval_amd.similarity import NccScorer
+
+    monkeypatch.setenv("SPR_NCC_FORCE_BIG", "1")
+    sc = NccScorer(method="fft", library=lib)
+    dev = sc.dev
+    c, h, w, nq, ng = 2, 32, 16, 3, 4
+    plan = sc.plan(c, (h, w), (h, w))
+    q = dev.to_device(np.stack([synth.gallery_features(97, 100 + i, c, h, w) for i in range(nq)]))
+    gal = [dev.to_device(np.stack([synth.gallery_features(97, 10 * k + i, c, h, w) for i in range(ng)])) for k in range(2)]
+    pq = sc.prepare_queries(plan, q)
+    want = []
+    for g in gal:  # reference: one stream, A then B
+        out = dev.zeros((nq, ng), np.float32)
+        sc.score_prepared(plan, pq, nq, sc.prepare_gallery(plan, g), ng, out, ng, 0)
+        want.append(dev.to_host(out))
+    assert not np.array_equal(want[0], want[1])
+    torch.cuda.synchronize()
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    got = [dev.zeros((nq, ng), np.float32) for _ in streams]
+    pg = [dev.empty_bytes(plan.gallery_item_bytes * ng) for _ in streams]  # each stream's own prepared buffer
+    torch.cuda.synchronize()
+    for _ in range(8):
+        for k, s in enumerate(streams):
+            with torch.cuda.stream(s):
+                sc.prepare_gallery(plan, gal[k], out=pg[k])
+                sc.score_prepared(plan, pq, nq, pg[k], ng, got[k], ng, 0)
+    for s in streams:
+        s.synchronize()
+    for k in range(2):
+        np.testing.assert_array_equal(dev.to_host(got[k]), want[k])
 
 
 def test_config3_bf16_resnet_layer3_maps(fft_scorer):
