@@ -443,6 +443,23 @@ int spr_resnet_trace_layout(const spr_resnet_plan* plan, int64_t n, int32_t in_h
 int spr_resnet_forward_trace(spr_resnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
                              int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
                              float* out, void* trace, spr_stream_t stream);
+/* Feature taps of the ResNet50, EfficientNet and DenseNet plans: spr_*_forward_taps is spr_*_forward (the same kernels, the
+ * same `out`, the same workspace) that also hands out the activation at n_taps further slice ends: tap_features[t] is an end
+ * into the backbone's children like the plan's block and strictly below it, tap_out[t] a device float32 [n, C_t, h_t, w_t]
+ * buffer of the caller's whose shape spr_*_tap_shape reports.  One pass then feeds a multi-layer score, as
+ * spr_vgg16_forward_taps does for the plain VGGs.
+ * The contract, for every family: the tap at end t of a plan truncated at block >= t is bit for bit the `out` of a plan of the
+ * same arch, compute type and parameters truncated at t.  In a 16-bit plan it is therefore the unrounded float32 value, and
+ * what the tapped layer stores for the next one is its rounding to the plan's type.  The block-end convolution stores both
+ * forms from the same accumulators (ResNet, EfficientNet); DenseNet's block tensors leave through the plan's closing kernel.
+ * Accepted ends - ResNet50: 5, 6 (layer1, layer2) below the block; EfficientNet: every stage end 2 .. block - 1 (not the stem
+ * alone); DenseNet_201: 5 .. block - 1.  Anything else, a tap named twice or a tap >= block: SPR_ERR_ARG with the accepted
+ * values in the message, and nothing is launched. */
+int spr_resnet_tap_shape(const spr_resnet_plan* plan, int32_t tap_feature, int32_t in_h, int32_t in_w, int32_t* channels,
+                         int32_t* out_h, int32_t* out_w);
+int spr_resnet_forward_taps(spr_resnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                            int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
+                            float* out, int32_t n_taps, const int32_t* tap_features, float* const* tap_out, spr_stream_t stream);
 
 /* ------------------------------------------------------------------ EfficientNetV2 feature extractor
  * network.py:163-175 (model choice), :185-186 (`list(model.features.children())[:block]`), :60-71 / :74-87 (transforms).
@@ -486,6 +503,12 @@ int spr_effnet_trace_layout(const spr_effnet_plan* plan, int64_t n, int32_t in_h
 int spr_effnet_forward_trace(spr_effnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
                              int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
                              float* out, void* trace, spr_stream_t stream);
+/* Feature taps (see spr_resnet_forward_taps): every stage end 2 .. block - 1 of model.features. */
+int spr_effnet_tap_shape(const spr_effnet_plan* plan, int32_t tap_feature, int32_t in_h, int32_t in_w, int32_t* channels,
+                         int32_t* out_h, int32_t* out_w);
+int spr_effnet_forward_taps(spr_effnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                            int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
+                            float* out, int32_t n_taps, const int32_t* tap_features, float* const* tap_out, spr_stream_t stream);
 
 /* ------------------------------------------------------------------ DenseNet_201 feature extractor
  * network.py:176-179, :185-186: torchvision's densenet201 `features` = [conv0, norm0, relu0, pool0, denseblock1, transition1,
@@ -534,6 +557,15 @@ int spr_densenet_trace_layout(const spr_densenet_plan* plan, int64_t n, int32_t 
 int spr_densenet_forward_trace(spr_densenet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
                                int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
                                float* out, void* trace, spr_stream_t stream);
+/* Feature taps (see spr_resnet_forward_taps): the ends 5 .. block - 1 of model.features (behind a dense block or a
+ * transition).  The tap is the plan's closing layout kernel launched on the live block tensor (behind a transition: on what
+ * the transition stored), so in a 16-bit plan it holds the stored values, as the truncated plan's output does. */
+int spr_densenet_tap_shape(const spr_densenet_plan* plan, int32_t tap_feature, int32_t in_h, int32_t in_w, int32_t* channels,
+                           int32_t* out_h, int32_t* out_w);
+int spr_densenet_forward_taps(spr_densenet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                              int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
+                              float* out, int32_t n_taps, const int32_t* tap_features, float* const* tap_out,
+                              spr_stream_t stream);
 
 /* ------------------------------------------------------------------ synthetic data
  * Bench/test support: the device twin of shoeprint_image_retrieval_amd/synth.py (bit-identical

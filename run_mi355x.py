@@ -9,7 +9,9 @@ the S-scores of that cluster against the whole-data-set totals.  Additionally pr
 clusters at the end.  With ``[mi355x] shortlist = K`` it also prints, under every query's rank line, the K best gallery
 prints with score, best query variant and the offset at which the mark lies on the print.  With ``[mi355x] device_resident = true``
 features and scores stay in device memory from the extractor to the ranks (features.FeatureSet): per cluster only the rank vector
-and the shortlist come back, the printed output and the ranks are the same.
+and the shortlist come back, the printed output and the ranks are the same.  With ``[mi355x] fuse_blocks = [..]`` (default []: off)
+a cluster whose block is b is scored on the feature layers {t in fuse_blocks : t < b} and b - one tapped extractor pass, one score
+matrix per layer, their mean on the device (``fused_ranks``); not together with ``shortlist`` or ``gallery_cache``.
 """
 
 import os
@@ -66,6 +68,23 @@ def _host_images(images):
     return images.to_host_list() if isinstance(images, DeviceImages) else images
 
 
+def fused_ranks(model, layers, shoemark_images, shoeprint_images, matching_shoeprint_ids, config):
+    """[mi355x] fuse_blocks: one tapped extractor pass per image batch hands out the feature layers ``layers`` (slice ends,
+    the model's block last), every layer is scored as usual (the maximum over the query variants) and the cluster's score is
+    the mean of the layers' matrices; features and scores stay in device memory, the rank vector comes back."""
+    comp = config["comparison"]
+    scorer = scorer_from_config(config)
+    shoemark_sets = model.get_multiple_feature_maps_device(shoemark_images, taps=layers)
+    shoeprint_sets = model.get_multiple_feature_maps_device(shoeprint_images, taps=layers)
+    print("Calculating ranks:")
+    scores = scorer.multi_layer_score_matrix_device(list(zip(shoemark_sets, shoeprint_sets)), rotations=comp.get("rotations"),
+                                                    scales=comp.get("scales"))
+    ranks = scorer.ranks_of_device(scores, matching_shoeprint_ids)
+    for i, r in enumerate(ranks):
+        print(f"Print {i} true match ranked {r}")
+    return ranks
+
+
 def main(config_file: str = "run.toml") -> list[int]:
     config = load_config(config_file)
     dataloader = Dataloader(config)
@@ -75,6 +94,14 @@ def main(config_file: str = "run.toml") -> list[int]:
     for cluster, (shoemark_images, shoeprint_images, matching_shoeprint_ids, block) in enumerate(dataloader):
         print(f"Cluster has {len(shoemark_images)} items.")
         model = Model(config, block)
+        fuse = config["mi355x"].get("fuse_blocks") or []
+        if fuse:
+            layers = sorted({t for t in fuse if t < block} | {block})
+            print(f"Scoring the feature layers {layers} of features[:{block}].")
+            ranks = fused_ranks(model, layers, shoemark_images, shoeprint_images, matching_shoeprint_ids, config)
+            cmp_all(list(ranks), total_shoeprints=len(dataloader.shoeprint_files), total_shoemarks=len(dataloader.shoemark_files))
+            all_ranks += [int(r) for r in ranks]
+            continue
         resident = bool(config["mi355x"].get("device_resident", False))
         if resident:
             need, ceiling = feature_bytes(model, shoemark_images, shoeprint_images), float(config["mi355x"].get("max_feature_gib", 64.0))

@@ -148,6 +148,11 @@ SIGNATURES = {
     "spr_resnet_trace_layout": (C.c_int, [_VP, _I64, _I32, _I32, C.POINTER(_I64), C.POINTER(_SZ)]),
     "spr_resnet_forward_trace": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                            _VP, _VP, _VP, _VP, _VP]),
+    **{f"spr_{fam}_tap_shape": (C.c_int, [_VP, _I32, _I32, _I32, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)])
+       for fam in ("resnet", "effnet", "densenet")},
+    **{f"spr_{fam}_forward_taps": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                             _VP, _VP, _VP, _I32, C.POINTER(_I32), C.POINTER(_VP), _VP])
+       for fam in ("resnet", "effnet", "densenet")},
     "spr_synth_gallery": (C.c_int, [_VP, _I64, _I64, _I32, _I32, _I32, C.c_uint64, _VP]),
     "spr_synth_queries": (C.c_int, [_VP, _I64, _I64, _VP, _I32, _I32, _I32, C.c_uint64, _I32, _I32, _I32, _VP]),
 }

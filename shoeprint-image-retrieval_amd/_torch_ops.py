@@ -6,6 +6,8 @@
 * ``ncc_scores(q, g, crop=2, method="auto", max_prepared_bytes=0) -> float32 [Q, G]``   (similarity.py:129-227)
 * ``ranks(scores, match) -> int32 [Q]``                                                (similarity.py:378-386)
 * ``extract(images, packed, arch, block, mean, std) -> float32 [N, C, h, w]``          (network.py:210-244, plain VGG)
+* ``extract_taps(images, packed, arch, block, mean, std, compute, taps) -> [float32 [N, C_t, h_t, w_t]..., out]``  (one pass, the
+  activations at the slice ends ``taps`` then the output; arch 0 .. 2 plain VGG, 16 + EfficientNet arch, 32 ResNet50, 48 DenseNet_201)
 * ``topk(scores, k) -> (float32 [Q, k], int32 [Q, k])``                                 (the k best items per row, ranker's order)
 * ``ncc_scores_located(q, g, crop=2, method="auto", max_prepared_bytes=0) -> (float32 [Q, G], int32 [Q, G, 2])``
   (``ncc_scores`` and the pixel at which every pair's NCC map peaks, (-1, -1) where the score is 0; "fft" / "direct" plans)

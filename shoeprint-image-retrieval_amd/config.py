@@ -54,6 +54,7 @@ class Mi355xConfig(TypedDict, total=False):
     max_decoded_gib: float  # with device_resize: decoded gallery images kept in device memory between clusters, at most
     device_resident: bool  # images (with device_resize), features and scores stay in device memory from the loader to the ranks
     max_feature_gib: float  # with device_resident: a cluster whose query + gallery features exceed it takes the host route
+    fuse_blocks: list[int]  # slice ends below a cluster's block whose score matrices are fused with the block's (mean); [] = off
 
 
 class Config(TypedDict, total=False):
@@ -66,7 +67,8 @@ class Config(TypedDict, total=False):
 MI355X_DEFAULTS: dict[str, Any] = {"dtype": "float32", "ncc_method": "auto", "max_prepared_gib": 0.0, "weights": "",
                                    "gallery_cache": "", "extractor_dtype": "float32", "f32_matrix_cores": False,
                                    "shortlist": 0, "device_resize": False, "max_decoded_gib": 8.0,
-                                   "matrix_core_peaks": False, "device_resident": False, "max_feature_gib": 64.0}
+                                   "matrix_core_peaks": False, "device_resident": False, "max_feature_gib": 64.0,
+                                   "fuse_blocks": []}
 
 
 def normalise(raw: dict) -> Config:
@@ -91,6 +93,25 @@ def normalise(raw: dict) -> Config:
     budget = extra["max_decoded_gib"]
     if isinstance(budget, bool) or not isinstance(budget, (int, float)) or budget < 0:
         raise ValueError(f"[mi355x].max_decoded_gib = {budget!r}: expected a number of GiB >= 0 (0 = keep nothing)")
+    fuse = extra["fuse_blocks"]
+    if not isinstance(fuse, list) or any(isinstance(t, bool) or not isinstance(t, int) for t in fuse):
+        raise ValueError(f"[mi355x].fuse_blocks = {fuse!r}: expected a list of integers ([] = off)")
+    if fuse:
+        from .network import tap_ends  # (the table of slice ends per backbone; nothing is loaded or built)
+
+        try:
+            accepted = tap_ends(str(raw.get("model", {}).get("type", "")))
+        except LookupError:
+            accepted = None  # (Model raises the reference's LookupError for the type itself)
+        bad = [t for t in fuse if accepted is not None and t not in accepted]
+        if bad:
+            raise ValueError(f"[mi355x].fuse_blocks = {fuse!r}: {bad} are not feature taps of {raw['model']['type']} "
+                             f"(slice ends {accepted})")
+        if shortlist > 0:
+            raise ValueError("[mi355x].fuse_blocks with shortlist > 0: located peaks are per layer, a shortlist on the fused "
+                             "score is not built")
+        if extra["gallery_cache"]:
+            raise ValueError("[mi355x].fuse_blocks with gallery_cache: cached galleries hold one layer")
     raw["mi355x"] = extra
     return raw  # type: ignore[return-value]
 

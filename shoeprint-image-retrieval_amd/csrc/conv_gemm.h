@@ -38,6 +38,10 @@ struct ConvCall {
   int act = 0;                      // 0 none, 1 ReLU (behind the residual sum), 2 SiLU (in front of it)
   void* out = nullptr;              // NHWC result ...
   float* out_nchw = nullptr;        // ... or, if not null, the float32 NCHW result [n][cout_real][ho][wo] (last layer)
+  float* tap_nchw = nullptr;        // a feature tap: beside the NHWC store into `out`, the same values - unrounded in a 16-bit
+                                    // plan - as float32 NCHW [n][tap_real][ho][wo], as out_nchw would hold them (not with it)
+  int tap_real = 0;                 // channels of tap_nchw; 0: cout_real, or cout where that is 0 too
+  int tap_channels() const { return tap_real ? tap_real : cout_real ? cout_real : cout; }
   int in_stride() const { return lda ? lda : cin; }
   int out_stride() const { return ldc ? ldc : cout; }
 };
@@ -61,7 +65,8 @@ int launch_stem16(int kind, int ks, int stride, const uint8_t* images, int64_t n
 // 3x3 / stride 2 / pad 1 max pool of an NHWC tensor [n][h][w][c] (ldo: channel stride of the output; 16-bit: a multiple of 8)
 int launch_maxpool3(const float* in, int64_t n, int h, int w, int c, float* out, int ldo, hipStream_t s);
 int launch_maxpool3_16(const uint16_t* in, int64_t n, int h, int w, int c, uint16_t* out, int ldo, hipStream_t s);
-// implicit-GEMM convolution on the f32 matrix cores: (ks, stride) in (1, 1), (1, 2), (3, 1), (3, 2); see conv_gemm_kernel
+// implicit-GEMM convolution on the f32 matrix cores: (ks, stride) in (1, 1), (1, 2), (3, 1), (3, 2); see conv_gemm_kernel.
+// This launcher and launch_conv_gemm16 honour tap_nchw (both stores out of one launch); the others refuse it
 int launch_conv_gemm(const ConvCall& c, hipStream_t s);
 // ... on the 16-bit matrix cores: the same four (ks, stride); see conv_gemm16_kernel (no lda / ldc / c_off / pre_s; cout_real
 // counts for the NCHW result only).  bn_switch: this call honours SPR_GEMM16_BN=128 (128-channel tiles where cout allows;
@@ -77,6 +82,24 @@ int launch_conv16_3x3(int kind, const ConvCall& c, hipStream_t s);
 // means there is nothing to do.
 int check_forward_args(const char* name, const void* plan, const void* images, int64_t n, int in_h, int in_w, int in_channels,
                        const float* mean3, const float* inv_std3, const void* packed, const void* workspace, const float* out);
+
+// ---- feature taps (spr_*_forward_taps): slice ends into the backbone's children, like the plan's block, and where the
+// float32 NCHW activation at each goes.  check_taps refuses (SPR_ERR_ARG, naming `accepted`) a null array, a tap that is not
+// in `accepted` (ascending; the backbone puts only ends below the plan's block there) and a tap named twice; a null
+// tap_out[t] is refused unless n == 0.
+struct TapSet {
+  std::vector<int> feature;
+  std::vector<float*> out;
+  float* find(int f) const {
+    for (size_t t = 0; t < feature.size(); ++t)
+      if (feature[t] == f) return out[t];
+    return nullptr;
+  }
+};
+int check_taps(const char* name, const std::vector<int>& accepted, int block, int32_t n_taps, const int32_t* tap_features,
+               float* const* tap_out, int64_t n, TapSet* set);
+// one tap end against `accepted` (spr_*_tap_shape)
+int check_tap(const char* name, const std::vector<int>& accepted, int block, int tap);
 
 // ---- trace records (spr_*_forward_trace): what a layer stored, copied device to device behind it on the same stream.
 // Records lie 256-byte aligned in plan order; NHWC [n][h][w][c] in the plan's compute type (16-bit or float32; c padded as

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <string>
 
 #include "conv_gemm.h"
 
@@ -143,7 +144,9 @@ __global__ void __launch_bounds__(kThreads, 2)
 conv_gemm_kernel(const float* __restrict__ in, int n_img, int H, int W, int cin, int cout, const float* __restrict__ wts,
                  const float* __restrict__ bias, const float* __restrict__ res, int relu, int nchw,
                  float* __restrict__ out, const float* __restrict__ in_scale, int cout_real, int lda, int ldc, int c_off,
-                 const float* __restrict__ pre_s, const float* __restrict__ pre_t) {
+                 const float* __restrict__ pre_s, const float* __restrict__ pre_t, float* __restrict__ tap, int tap_real) {
+  // tap: null, or (with an NHWC `out`) where the first tap_real channels of the same result also go as float32 NCHW
+  // [n][tap_real][Ho][Wo] - a feature tap, the values an NCHW `out` of a plan that ends here would hold
   // lda / ldc: channel strides of the input / NHWC output tensors (>= cin / cout: a convolution may read a prefix of a wider
   // tensor and write a channel range [c_off, c_off + cout_real) of one - DenseNet's concatenation); pre_s / pre_t: per input
   // channel, max(x * s + t, 0) applied while the operand is loaded (BatchNorm + ReLU in FRONT of a 1x1 convolution), or null
@@ -236,6 +239,11 @@ conv_gemm_kernel(const float* __restrict__ in, int n_img, int H, int W, int cin,
         out[((img * creal + ch) * Ho + oy) * static_cast<size_t>(Wo) + ox] = v;
       } else if (!cout_real || ch < cout_real) {
         out[static_cast<size_t>(m) * ldc + c_off + ch] = v;
+      }
+      if (tap && ch < tap_real) {
+        const int ox = static_cast<int>(m % Wo), oy = static_cast<int>((m / Wo) % Ho);
+        const size_t img = static_cast<size_t>(m / (static_cast<long long>(Wo) * Ho));
+        tap[((img * tap_real + ch) * Ho + oy) * static_cast<size_t>(Wo) + ox] = v;
       }
     }
   }
@@ -465,7 +473,9 @@ __global__ void __launch_bounds__(kThreads, BN == 128 ? 2 : 3)
 conv_gemm16_kernel(const uint16_t* __restrict__ in, int n_img, int H, int W, int cin, int cout,
                    const uint16_t* __restrict__ wts, const float* __restrict__ bias, const uint16_t* __restrict__ res,
                    int relu, uint16_t* __restrict__ out, float* __restrict__ out32, const float* __restrict__ in_scale,
-                   int cout_real) {
+                   int cout_real, float* __restrict__ tap) {
+  // tap: null, or (with out32 null) where the result also goes as float32 NCHW [n][cout_real][Ho][Wo], exactly as out32
+  // would hold it - a feature tap: the unrounded values whose round16 the NHWC store writes
   // relu: activation code (0 none, 1 ReLU behind the residual sum: ResNet bottlenecks, 2 SiLU in FRONT of it: EfficientNet
   // blocks); in_scale: [image][cin] f32 factors on the input (squeeze-excitation), applied while the operand is staged and
   // rounded again, or null; cout_real: channels of a float32 NCHW result when cout is padded (0: all of them)
@@ -599,7 +609,8 @@ conv_gemm16_kernel(const uint16_t* __restrict__ in, int n_img, int H, int W, int
       }
     }
     __syncthreads();
-    if (out32) {
+    // the float32 NCHW store of this half of the tile: the output of the last layer, or a feature tap beside the NHWC store
+    auto store_nchw = [&](float* __restrict__ dst) {
       // thread = (pixel row of the tile, half of the channels): for one channel, 128 consecutive work-items store 128
       // consecutive pixels of its plane
       const int row = tid & 127, c0 = tid >> 7;
@@ -617,9 +628,12 @@ conv_gemm16_kernel(const uint16_t* __restrict__ in, int n_img, int H, int W, int
           if (relu == 2) v = v / (1.0f + expf(-v));
           if (res) v += value16<KIND>(res[static_cast<size_t>(m) * cout + chn]);
           if (relu == 1) v = fmaxf(v, 0.0f);
-          out32[(img * creal + chn) * plane + pix] = v;
+          dst[(img * creal + chn) * plane + pix] = v;
         }
       }
+    };
+    if (out32) {
+      store_nchw(out32);
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -647,6 +661,7 @@ conv_gemm16_kernel(const uint16_t* __restrict__ in, int n_img, int H, int W, int
         }
         *reinterpret_cast<u32x4*>(out + at) = o;
       }
+      if (tap) store_nchw(tap);  // (the tile stays as it is until the next half's barrier)
     }
   }
 }
@@ -725,12 +740,14 @@ int launch_conv_gemm(const ConvCall& c, hipStream_t s) {
                 : c.ks == 3 && c.stride == 2 ? conv_gemm_kernel<3, 2>
                                              : nullptr;
   if (!kernel) { set_error("launch_conv_gemm: no %d x %d / stride %d instance", c.ks, c.ks, c.stride); return SPR_ERR_UNSUPPORTED; }
+  if (c.tap_nchw && c.out_nchw) { set_error("launch_conv_gemm: a feature tap goes beside an NHWC result"); return SPR_ERR_UNSUPPORTED; }
   const long long m = static_cast<long long>(c.n) * out_size(c.h, c.ks, c.stride) * out_size(c.w, c.ks, c.stride);
   float* out = c.out_nchw ? c.out_nchw : static_cast<float*>(c.out);
   hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((m + kGM - 1) / kGM), static_cast<unsigned>(c.cout / kGN)), dim3(kThreads),
                      0, s, static_cast<const float*>(c.in), static_cast<int>(c.n), c.h, c.w, c.cin, c.cout,
                      static_cast<const float*>(c.wts), c.bias, static_cast<const float*>(c.res), c.act, c.out_nchw ? 1 : 0, out,
-                     c.in_scale, c.cout_real, c.in_stride(), c.out_stride(), c.c_off, c.pre_s, c.pre_t);
+                     c.in_scale, c.cout_real, c.in_stride(), c.out_stride(), c.c_off, c.pre_s, c.pre_t, c.tap_nchw,
+                     c.tap_channels());
   return check_launch("conv_gemm_kernel");
 }
 
@@ -745,6 +762,11 @@ auto gemm16_kernel_of(int kind) {
 int launch_conv_gemm16(int kind, const ConvCall& c, bool bn_switch, hipStream_t s) {
   if (c.in_stride() != c.cin || c.out_stride() != c.cout || c.c_off != 0 || c.pre_s || c.pre_t) {
     set_error("launch_conv_gemm16: conv_gemm16_kernel has no channel strides, channel offset or operand BatchNorm");
+    return SPR_ERR_UNSUPPORTED;
+  }
+  // the tap store reads the residual operand again behind the NHWC store: the two tensors must not be one
+  if (c.tap_nchw && (c.out_nchw || c.res == c.out)) {
+    set_error("launch_conv_gemm16: a feature tap goes beside an NHWC result that is not the residual operand");
     return SPR_ERR_UNSUPPORTED;
   }
   // 128-channel tiles only on request (SPR_GEMM16_BN=128; tests and A/B runs)
@@ -762,10 +784,13 @@ int launch_conv_gemm16(int kind, const ConvCall& c, bool bn_switch, hipStream_t 
     return SPR_ERR_UNSUPPORTED;
   }
   const long long m = static_cast<long long>(c.n) * out_size(c.h, ks, stride) * out_size(c.w, ks, stride);
+  // (the kernel reads cout_real in its NCHW store alone - the 16-bit NHWC store always writes all cout channels - so with a
+  // tap that argument carries the tap's channel count)
   hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((m + kHM - 1) / kHM), static_cast<unsigned>(c.cout / (wide ? 128 : 64))),
                      dim3(kThreads), 0, s, static_cast<const uint16_t*>(c.in), static_cast<int>(c.n), c.h, c.w, c.cin, c.cout,
                      static_cast<const uint16_t*>(c.wts), c.bias, static_cast<const uint16_t*>(c.res), c.act,
-                     static_cast<uint16_t*>(c.out), c.out_nchw, c.in_scale, c.cout_real);
+                     static_cast<uint16_t*>(c.out), c.out_nchw, c.in_scale, c.tap_nchw ? c.tap_channels() : c.cout_real,
+                     c.tap_nchw);
   return check_launch("conv_gemm16_kernel");
 }
 
@@ -779,6 +804,38 @@ int check_forward_args(const char* name, const void* plan, const void* images, i
   if (n != 0 && (!images || !mean3 || !inv_std3 || !packed || !out || !workspace)) {
     set_error("%s: null pointer", name);
     return SPR_ERR_ARG;
+  }
+  return SPR_OK;
+}
+
+namespace {
+std::string tap_list(const std::vector<int>& accepted) {
+  std::string list;
+  for (int a : accepted) list += (list.empty() ? "" : ", ") + std::to_string(a);
+  return list;
+}
+}  // namespace
+
+int check_tap(const char* name, const std::vector<int>& accepted, int block, int tap) {
+  if (std::find(accepted.begin(), accepted.end(), tap) != accepted.end()) return SPR_OK;
+  set_error("%s: tap %d: the taps of this plan (block %d) are the slice ends {%s}", name, tap, block, tap_list(accepted).c_str());
+  return SPR_ERR_ARG;
+}
+
+int check_taps(const char* name, const std::vector<int>& accepted, int block, int32_t n_taps, const int32_t* tap_features,
+               float* const* tap_out, int64_t n, TapSet* set) {
+  if (n_taps < 0 || (n_taps > 0 && (!tap_features || !tap_out))) { set_error("%s: bad tap arrays", name); return SPR_ERR_ARG; }
+  for (int32_t t = 0; t < n_taps; ++t) {
+    const int rc = check_tap(name, accepted, block, tap_features[t]);
+    if (rc != SPR_OK) return rc;
+    if (std::find(set->feature.begin(), set->feature.end(), tap_features[t]) != set->feature.end()) {
+      set_error("%s: tap %d named twice: each of the slice ends {%s} (block %d) at most once", name, tap_features[t],
+                tap_list(accepted).c_str(), block);
+      return SPR_ERR_ARG;
+    }
+    if (n != 0 && !tap_out[t]) { set_error("%s: null buffer for tap %d", name, tap_features[t]); return SPR_ERR_ARG; }
+    set->feature.push_back(tap_features[t]);
+    set->out.push_back(tap_out[t]);
   }
   return SPR_OK;
 }

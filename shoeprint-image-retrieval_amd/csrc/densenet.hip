@@ -434,7 +434,7 @@ auto dnet_gemm16_of(int kind) {
 // one convolution of a 16-bit plan: 1x1 with 64-channel tiles (cout a multiple of 64) or 3x3 -> 32 channels; stride 1, ReLU
 // or nothing behind it, NHWC out
 int launch_dnet_gemm16(int kind, const ConvCall& c, hipStream_t s) {
-  if (c.stride != 1 || c.res || c.in_scale || c.out_nchw || c.cout_real || c.act > 1 || !c.pre_s != !c.pre_t) {
+  if (c.stride != 1 || c.res || c.in_scale || c.out_nchw || c.tap_nchw || c.cout_real || c.act > 1 || !c.pre_s != !c.pre_t) {
     set_error("launch_dnet_gemm16: dnet_gemm16_kernel has no stride, residual, input factors, SiLU, NCHW result or padded cout");
     return SPR_ERR_UNSUPPORTED;
   }
@@ -490,8 +490,8 @@ TraceLayout densenet_trace_layout(const spr_densenet_plan* plan, int64_t n, int 
 // forward), or where the records of densenet_trace_layout are copied
 static int densenet_forward(spr_densenet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
                             int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
-                            float* out, spr_stream_t stream, unsigned char* trace) {
-  const int ok = check_forward_args("spr_densenet_forward", plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed,
+                            float* out, spr_stream_t stream, unsigned char* trace, const TapSet* taps = nullptr) {
+  const int ok = check_forward_args(taps ? "spr_densenet_forward_taps" : "spr_densenet_forward", plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed,
                                     workspace, out);
   if (ok != SPR_OK || n == 0) return ok;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -539,6 +539,19 @@ static int densenet_forward(spr_densenet_plan* plan, const uint8_t* images, int6
       if (rc != SPR_OK) return rc;
     }
   }
+  // the closing layout change: c channels of the live tensor (channel stride ld) -> float32 NCHW, the closing BatchNorm on the
+  // way where sc is given; also a feature tap's kernel, on the block tensor as it stands behind a dense block / a transition
+  auto to_nchw = [&](const void* src, const float* sc, const float* sh, float* dst) {
+    const size_t total = static_cast<size_t>(n) * c * h * w;
+    if (f32) {
+      hipLaunchKernelGGL(dnet_out_kernel, blocks_of(total), dim3(kThreads), 0, s, static_cast<const float*>(src), h * w, c, ld, sc,
+                         sh, 0, dst, total);
+    } else {
+      hipLaunchKernelGGL(f16 ? dnet_out16_kernel<SPR_F16> : dnet_out16_kernel<SPR_BF16>, blocks_of(total), dim3(kThreads), 0, s,
+                         static_cast<const uint16_t*>(src), h * w, c, ld, sc, sh, dst, total);
+    }
+    return check_launch(f32 ? "dnet_out_kernel" : "dnet_out16_kernel");
+  };
   const float* fin_s = nullptr;
   const float* fin_t = nullptr;
   for (size_t i = 1; i < plan->ops.size(); ++i) {
@@ -571,16 +584,15 @@ static int densenet_forward(spr_densenet_plan* plan, const uint8_t* images, int6
       fin_s = pk + o.s_off; fin_t = pk + o.t_off;
     }
     if (rc != SPR_OK) return rc;
+    // the last layer of child o.feature of `features`: features[:o.feature + 1] ends here
+    if (taps && i + 1 < plan->ops.size() && plan->ops[i + 1].feature != o.feature) {
+      if (float* tap = taps->find(o.feature + 1)) {
+        rc = to_nchw(cat, nullptr, nullptr, tap);
+        if (rc != SPR_OK) return rc;
+      }
+    }
   }
-  const size_t total = static_cast<size_t>(n) * c * h * w;
-  if (f32) {
-    hipLaunchKernelGGL(dnet_out_kernel, blocks_of(total), dim3(kThreads), 0, s, static_cast<const float*>(cat), h * w, c, ld, fin_s,
-                       fin_t, 0, out, total);
-  } else {
-    hipLaunchKernelGGL(f16 ? dnet_out16_kernel<SPR_F16> : dnet_out16_kernel<SPR_BF16>, blocks_of(total), dim3(kThreads), 0, s,
-                       static_cast<const uint16_t*>(cat), h * w, c, ld, fin_s, fin_t, out, total);
-  }
-  rc = check_launch(f32 ? "dnet_out_kernel" : "dnet_out16_kernel");
+  rc = to_nchw(cat, fin_s, fin_t, out);
   if (rc == SPR_OK) rc = trace_copy(trace, &lay, rec++, out, s);
   return rc;
 }
@@ -589,6 +601,39 @@ extern "C" int spr_densenet_forward(spr_densenet_plan* plan, const uint8_t* imag
                                     int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
                                     void* workspace, float* out, spr_stream_t stream) {
   return densenet_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, stream, nullptr);
+}
+
+// the accepted taps of a plan: the ends behind a dense block or a transition, below its block
+static std::vector<int> densenet_taps(const spr_densenet_plan* plan) {
+  std::vector<int> ends;
+  for (int t = 5; t < plan->block; ++t) ends.push_back(t);
+  return ends;
+}
+
+extern "C" int spr_densenet_tap_shape(const spr_densenet_plan* plan, int32_t tap_feature, int32_t in_h, int32_t in_w,
+                                      int32_t* channels, int32_t* out_h, int32_t* out_w) {
+  if (!plan || !channels || !out_h || !out_w || in_h < 1 || in_w < 1) { set_error("spr_densenet_tap_shape: bad argument"); return SPR_ERR_ARG; }
+  const int rc = check_tap("spr_densenet_tap_shape", densenet_taps(plan), plan->block, tap_feature);
+  if (rc != SPR_OK) return rc;
+  int hh = ((in_h + 1) / 2 + 1) / 2, ww = ((in_w + 1) / 2 + 1) / 2, cc = 64;  // (densenet_dims over features[:tap_feature])
+  for (const DOp& o : plan->ops) {
+    if (o.feature >= tap_feature) break;
+    if (o.kind == 2) cc = o.c_off + 32;
+    if (o.kind == 3) { hh /= 2; ww /= 2; cc = o.cout; }
+  }
+  *channels = cc; *out_h = hh; *out_w = ww;
+  return SPR_OK;
+}
+
+extern "C" int spr_densenet_forward_taps(spr_densenet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                                         int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
+                                         void* workspace, float* out, int32_t n_taps, const int32_t* tap_features,
+                                         float* const* tap_out, spr_stream_t stream) {
+  if (!plan) { set_error("spr_densenet_forward_taps: null plan"); return SPR_ERR_ARG; }
+  TapSet taps;
+  const int rc = check_taps("spr_densenet_forward_taps", densenet_taps(plan), plan->block, n_taps, tap_features, tap_out, n, &taps);
+  if (rc != SPR_OK) return rc;
+  return densenet_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, stream, nullptr, &taps);
 }
 
 extern "C" int spr_densenet_trace_layout(const spr_densenet_plan* plan, int64_t n, int32_t in_h, int32_t in_w, int64_t* records,

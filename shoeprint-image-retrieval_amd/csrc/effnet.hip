@@ -435,11 +435,12 @@ extern "C" int spr_effnet_trace_layout(const spr_effnet_plan* plan, int64_t n, i
 // instance, every other convolution on conv_gemm16_kernel.  Both: SiLU in front of the residual sum, squeeze-excitation
 // factors on the operand, depthwise convolutions and the squeeze-excitation mean on their kernels per type; float32 NCHW out.
 // trace: null (the plain forward), or where every layer's stored result is copied (effnet_trace_layout)
+// taps: null, or the stage ends whose block-end convolution also stores its float32 NCHW result (effnet_taps)
 static int effnet_forward(const spr_effnet_plan* plan, const uint8_t* images, int64_t n, int in_h, int in_w, int in_channels,
                           const float* mean3, const float* inv_std3, const void* packed, void* workspace, float* out,
-                          spr_stream_t stream, unsigned char* trace) {
-  const int ok = check_forward_args(trace ? "spr_effnet_forward_trace" : "spr_effnet_forward", plan, images, n, in_h, in_w,
-                                    in_channels, mean3, inv_std3, packed, workspace, out);
+                          spr_stream_t stream, unsigned char* trace, const TapSet* taps = nullptr) {
+  const int ok = check_forward_args(trace ? "spr_effnet_forward_trace" : taps ? "spr_effnet_forward_taps" : "spr_effnet_forward",
+                                    plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out);
   if (ok != SPR_OK || n == 0) return ok;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const float* pk = static_cast<const float*>(packed);
@@ -488,6 +489,10 @@ static int effnet_forward(const spr_effnet_plan* plan, const uint8_t* images, in
       k.cout_real = f32 && !last ? 0 : o.cout;  // (an f32 NHWC store honours it: the padded channels must be written)
       k.in = cur; k.wts = pk + o.w_off; k.bias = pk + o.b_off; k.res = o.res ? x : nullptr; k.in_scale = o.scaled ? scale : nullptr;
       k.act = o.act; k.out = dst; k.out_nchw = last ? out : nullptr;
+      if (taps && o.block_end && !last && plan->ops[i + 1].feature != o.feature) {  // a stage's end: features[:feature + 1]
+        k.tap_nchw = taps->find(o.feature + 1);
+        k.tap_real = o.cout;
+      }
       rc = f32 ? launch_conv_gemm(k, s) : launch_conv_gemm16(kind, k, false, s);
       if (rc == SPR_OK) rc = trace_copy(trace, &lay, i, last ? static_cast<void*>(out) : dst, s);
       if (rc != SPR_OK) return rc;
@@ -535,6 +540,40 @@ static int effnet_forward(const spr_effnet_plan* plan, const uint8_t* images, in
     }
   }
   return SPR_OK;
+}
+
+// the accepted taps of a plan: every stage end below its block (a stage's last layer is a block-end convolution)
+static std::vector<int> effnet_taps(const spr_effnet_plan* plan) {
+  std::vector<int> ends;
+  for (int t = 2; t < plan->block; ++t) ends.push_back(t);
+  return ends;
+}
+
+extern "C" int spr_effnet_tap_shape(const spr_effnet_plan* plan, int32_t tap_feature, int32_t in_h, int32_t in_w,
+                                    int32_t* channels, int32_t* out_h, int32_t* out_w) {
+  if (!plan || !channels || !out_h || !out_w || in_h < 1 || in_w < 1) { set_error("spr_effnet_tap_shape: bad argument"); return SPR_ERR_ARG; }
+  const int rc = check_tap("spr_effnet_tap_shape", effnet_taps(plan), plan->block, tap_feature);
+  if (rc != SPR_OK) return rc;
+  int hh = in_h, ww = in_w, cc = 3;
+  for (const EOp& o : plan->ops) {  // (effnet_dims over features[:tap_feature])
+    if (o.feature >= tap_feature) break;
+    if (o.kind == 2) continue;
+    if (o.stride == 2) { hh = (hh - 1) / 2 + 1; ww = (ww - 1) / 2 + 1; }
+    cc = o.cout;
+  }
+  *channels = cc; *out_h = hh; *out_w = ww;
+  return SPR_OK;
+}
+
+extern "C" int spr_effnet_forward_taps(spr_effnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                                       int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
+                                       void* workspace, float* out, int32_t n_taps, const int32_t* tap_features,
+                                       float* const* tap_out, spr_stream_t stream) {
+  if (!plan) { set_error("spr_effnet_forward_taps: null plan"); return SPR_ERR_ARG; }
+  TapSet taps;
+  const int rc = check_taps("spr_effnet_forward_taps", effnet_taps(plan), plan->block, n_taps, tap_features, tap_out, n, &taps);
+  if (rc != SPR_OK) return rc;
+  return effnet_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, stream, nullptr, &taps);
 }
 
 extern "C" int spr_effnet_forward_trace(spr_effnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,

@@ -178,10 +178,11 @@ extern "C" size_t spr_resnet_workspace_bytes(const spr_resnet_plan* plan, int64_
 // stride 1 layers and conv_gemm16_kernel for the others (the only call sites that honour SPR_GEMM16_BN).  out_nchw: null, or
 // where the last layer's float32 NCHW result goes
 static int resnet_conv(const spr_resnet_plan* plan, const RConv& c, const void* in, int64_t n, int h, int w, const float* pk,
-                       const void* res, void* out, float* out_nchw, hipStream_t s) {
+                       const void* res, void* out, float* out_nchw, hipStream_t s, float* tap = nullptr) {
   ConvCall k;
   k.ks = c.ks; k.stride = c.stride; k.n = n; k.h = h; k.w = w; k.cin = c.cin; k.cout = c.cout;
   k.in = in; k.wts = pk + c.w_off; k.bias = pk + c.b_off; k.res = res; k.act = c.relu; k.out = out; k.out_nchw = out_nchw;
+  k.tap_nchw = tap;  // (a layer's last conv3: a 1x1 convolution, never on the patch kernel)
   if (plan->compute == SPR_F32) return launch_conv_gemm(k, s);
   if (c.ks == 3 && c.stride == 1) return launch_conv16_3x3(plan->compute, k, s);
   return launch_conv_gemm16(plan->compute, k, true, s);
@@ -221,8 +222,8 @@ extern "C" int spr_resnet_trace_layout(const spr_resnet_plan* plan, int64_t n, i
 // result is copied (resnet_trace_layout: record 1 + conv index)
 static int resnet_forward(spr_resnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
                           int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed, void* workspace,
-                          float* out, spr_stream_t stream, unsigned char* trace) {
-  const int ok = check_forward_args("spr_resnet_forward", plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed,
+                          float* out, spr_stream_t stream, unsigned char* trace, const TapSet* taps = nullptr) {
+  const int ok = check_forward_args(taps ? "spr_resnet_forward_taps" : "spr_resnet_forward", plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed,
                                     workspace, out);
   if (ok != SPR_OK || n == 0) return ok;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -257,6 +258,7 @@ static int resnet_forward(spr_resnet_plan* plan, const uint8_t* images, int64_t 
     h = (h + 1) / 2; w = (w + 1) / 2;
   }
   size_t i = 1;
+  int layer = 0;  // layers begun
   while (i < plan->convs.size()) {  // one bottleneck
     const RConv& c1 = plan->convs[i];
     const RConv& c2 = plan->convs[i + 1];
@@ -277,7 +279,12 @@ static int resnet_forward(spr_resnet_plan* plan, const uint8_t* images, int64_t 
       if (rc != SPR_OK) return rc;
       resid = t1;
     }
-    rc = resnet_conv(plan, c3, t2, n, ho, wo, pk, resid, y, last ? out : nullptr, s);
+    // the last bottleneck of a layer (the next one opens with a downsample branch) ends child 4 + layer of the list
+    if (down) ++layer;
+    const size_t next = i + (down ? 4 : 3);
+    float* tap = nullptr;
+    if (taps && !last && plan->convs[next + 2].res == 2) tap = taps->find(4 + layer);
+    rc = resnet_conv(plan, c3, t2, n, ho, wo, pk, resid, y, last ? out : nullptr, s, tap);
     if (rc == SPR_OK) rc = trace_copy(trace, &lay, 3 + i, last ? static_cast<void*>(out) : y, s);
     if (rc != SPR_OK) return rc;
     h = ho; w = wo;
@@ -291,6 +298,35 @@ extern "C" int spr_resnet_forward(spr_resnet_plan* plan, const uint8_t* images, 
                                   int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
                                   void* workspace, float* out, spr_stream_t stream) {
   return resnet_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, stream, nullptr);
+}
+
+// the accepted taps of a plan: the layer ends below its block
+static std::vector<int> resnet_taps(const spr_resnet_plan* plan) {
+  std::vector<int> ends;
+  for (int t = 5; t < plan->block; ++t) ends.push_back(t);
+  return ends;
+}
+
+extern "C" int spr_resnet_tap_shape(const spr_resnet_plan* plan, int32_t tap_feature, int32_t in_h, int32_t in_w,
+                                    int32_t* channels, int32_t* out_h, int32_t* out_w) {
+  if (!plan || !channels || !out_h || !out_w || in_h < 1 || in_w < 1) { set_error("spr_resnet_tap_shape: bad argument"); return SPR_ERR_ARG; }
+  const int rc = check_tap("spr_resnet_tap_shape", resnet_taps(plan), plan->block, tap_feature);
+  if (rc != SPR_OK) return rc;
+  spr_resnet_plan cut{};  // (resnet_dims reads the block alone)
+  cut.block = tap_feature;
+  resnet_dims(&cut, in_h, in_w, channels, out_h, out_w);
+  return SPR_OK;
+}
+
+extern "C" int spr_resnet_forward_taps(spr_resnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,
+                                       int32_t in_channels, const float* mean3, const float* inv_std3, const void* packed,
+                                       void* workspace, float* out, int32_t n_taps, const int32_t* tap_features,
+                                       float* const* tap_out, spr_stream_t stream) {
+  if (!plan) { set_error("spr_resnet_forward_taps: null plan"); return SPR_ERR_ARG; }
+  TapSet taps;
+  const int rc = check_taps("spr_resnet_forward_taps", resnet_taps(plan), plan->block, n_taps, tap_features, tap_out, n, &taps);
+  if (rc != SPR_OK) return rc;
+  return resnet_forward(plan, images, n, in_h, in_w, in_channels, mean3, inv_std3, packed, workspace, out, stream, nullptr, &taps);
 }
 
 extern "C" int spr_resnet_forward_trace(spr_resnet_plan* plan, const uint8_t* images, int64_t n, int32_t in_h, int32_t in_w,

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime_api.h>
 #include <torch/library.h>
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <string>
@@ -196,6 +197,19 @@ std::tuple<at::Tensor, at::Tensor> topk(const at::Tensor& scores, int64_t k) {
   return {out_scores, out_index};
 }
 
+// the plan cache of `extract` and `extract_taps` (plain VGGs)
+spr_vgg16_plan* vgg_plan(int device, int64_t arch, int64_t block, int64_t compute) {
+  std::lock_guard<std::mutex> lock(g_mutex);
+  const auto key = std::make_tuple(device, static_cast<int>(arch), static_cast<int>(block), static_cast<int>(compute));
+  auto it = g_vgg_plans.find(key);
+  if (it != g_vgg_plans.end()) return it->second;
+  spr_vgg16_plan* plan = nullptr;
+  check(spr_vgg_plan_create_ex(static_cast<int32_t>(arch), static_cast<int32_t>(block), static_cast<int32_t>(compute), &plan),
+        "extract (plan)");
+  g_vgg_plans[key] = plan;
+  return plan;
+}
+
 // features[:block] of a plain VGG (arch 0 VGG16, 1 VGG19, 2 VGG19_BN; network.py:121-139, :185-186) on a uint8 batch
 // [N,H,W] (grey, repeated over three planes: network.py:67) or [N,H,W,3]; `packed` = the weights as spr_vgg16_pack_weights
 // wrote them; mean / std as the reference's transforms take them (network.py:60-71); compute = spr_dtype of the plan
@@ -208,20 +222,7 @@ at::Tensor extract(const at::Tensor& images, const at::Tensor& packed, int64_t a
               "images are uint8 [N, H, W] or [N, H, W, 3]");
   TORCH_CHECK(mean.size() == 3 && std_.size() == 3, "mean and std hold three values");
   const DeviceGuard guard(images.device());
-  spr_vgg16_plan* plan = nullptr;
-  {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    const auto key = std::make_tuple(static_cast<int>(images.device().index()), static_cast<int>(arch), static_cast<int>(block),
-                                     static_cast<int>(compute));
-    auto it = g_vgg_plans.find(key);
-    if (it == g_vgg_plans.end()) {
-      check(spr_vgg_plan_create_ex(static_cast<int32_t>(arch), static_cast<int32_t>(block), static_cast<int32_t>(compute), &plan),
-            "extract (plan)");
-      g_vgg_plans[key] = plan;
-    } else {
-      plan = it->second;
-    }
-  }
+  spr_vgg16_plan* plan = vgg_plan(images.device().index(), arch, block, compute);
   TORCH_CHECK(static_cast<size_t>(packed.numel()) * packed.element_size() >= spr_vgg16_packed_bytes(plan),
               "packed weights: ", packed.numel() * packed.element_size(), " bytes, the plan needs ", spr_vgg16_packed_bytes(plan));
   const int64_t n = images.size(0);
@@ -239,9 +240,157 @@ at::Tensor extract(const at::Tensor& images, const at::Tensor& packed, int64_t a
   return out;
 }
 
+// ---- extract_taps: one extractor pass that also hands out the activations at `taps` (slice ends like `block`, strictly below
+// it, each once; Model.extract_taps_device) -> the taps in the order asked, then `out`.  arch names the backbone:
+//   0 .. 2    plain VGG (spr_vgg_arch, as `extract`; the plan cache of `extract`): spr_vgg16_forward_taps
+//   16 + a    EfficientNet arch a of spr_effnet_plan_create (16 = EfficientNetV2_S, 17 = _M ...): spr_effnet_forward_taps
+//   32        ResNet50: spr_resnet_forward_taps          48   DenseNet_201: spr_densenet_forward_taps
+// `packed`: the plan's packed parameters as the host mirror builds them (Model.packed).
+constexpr int64_t kArchEffnet = 16, kArchResnet = 32, kArchDensenet = 48;
+std::map<std::tuple<int, int, int, int>, void*> g_backbone_plans;  // device, arch code, block, compute type
+
+struct TapCall {
+  const at::Tensor& images;
+  const at::Tensor& packed;
+  float mean3[3], inv3[3];
+  int64_t n;
+  int32_t h, w, ch;
+};
+
+at::Tensor f32_like(const at::Tensor& images, int64_t n, int32_t c, int32_t h, int32_t w) {
+  return at::empty({n, c, h, w}, images.options().dtype(at::kFloat));
+}
+
+// ResNet50 / EfficientNet / DenseNet_201: their entry points share one calling sequence
+template <class Plan, class Shape, class TapShape, class Ws, class Fwd>
+std::vector<at::Tensor> backbone_taps(Plan* plan, size_t packed_bytes, Shape output_shape, TapShape tap_shape, Ws workspace_bytes,
+                                      Fwd forward_taps, const TapCall& a, const std::vector<int64_t>& taps) {
+  TORCH_CHECK(static_cast<size_t>(a.packed.numel()) * a.packed.element_size() >= packed_bytes, "packed weights: ",
+              a.packed.numel() * a.packed.element_size(), " bytes, the plan needs ", packed_bytes);
+  int32_t c = 0, oh = 0, ow = 0;
+  check(output_shape(plan, a.h, a.w, &c, &oh, &ow), "extract_taps (shape)");
+  std::vector<at::Tensor> result;
+  std::vector<int32_t> ends;
+  std::vector<float*> ptrs;
+  for (int64_t t : taps) {
+    int32_t tc = 0, th = 0, tw = 0;
+    check(tap_shape(plan, static_cast<int32_t>(t), a.h, a.w, &tc, &th, &tw), "extract_taps (tap)");  // refuses a bad tap
+    result.push_back(f32_like(a.images, a.n, tc, th, tw));
+    ends.push_back(static_cast<int32_t>(t));
+    ptrs.push_back(a.n ? result.back().template data_ptr<float>() : nullptr);
+  }
+  at::Tensor out = f32_like(a.images, a.n, c, oh, ow);
+  if (a.n != 0) {
+    at::Tensor ws = at::empty({static_cast<int64_t>(std::max<size_t>(16, workspace_bytes(plan, a.n, a.h, a.w)))},
+                              a.images.options().dtype(at::kByte));
+    check(forward_taps(plan, a.images.template data_ptr<uint8_t>(), a.n, a.h, a.w, a.ch, a.mean3, a.inv3, a.packed.data_ptr(),
+                       ws.data_ptr(), out.template data_ptr<float>(), static_cast<int32_t>(ends.size()), ends.data(), ptrs.data(),
+                       current_stream(a.images)), "extract_taps");
+  }
+  result.push_back(out);
+  return result;
+}
+
+// plain VGG: spr_vgg16_forward_taps names convolutions; the convolution whose ReLU ends features[:t], and its output size
+// (the image halved once per max pool in front of it), from spr_vgg_conv_info as Model.extract_taps_device finds them
+std::vector<at::Tensor> vgg_taps(spr_vgg16_plan* plan, int64_t block, const TapCall& a, const std::vector<int64_t>& taps) {
+  TORCH_CHECK(static_cast<size_t>(a.packed.numel()) * a.packed.element_size() >= spr_vgg16_packed_bytes(plan),
+              "packed weights: ", a.packed.numel() * a.packed.element_size(), " bytes, the plan needs ", spr_vgg16_packed_bytes(plan));
+  const int convs = spr_vgg16_num_convs(plan);
+  std::vector<int32_t> at_feature(convs), bn(convs);
+  for (int i = 0; i < convs; ++i) check(spr_vgg_conv_info(plan, i, &at_feature[i], &bn[i]), "extract_taps (plan)");
+  std::vector<at::Tensor> result;
+  std::vector<int32_t> ordinals;
+  std::vector<float*> ptrs;
+  for (int64_t t : taps) {
+    TORCH_CHECK(t < block, "extract_taps: tap ", t, " is not below the block (", block, "): the output comes last anyway");
+    int conv = -1;
+    for (int i = 1; i < convs; ++i)
+      if (at_feature[i] + (bn[i] ? 2 : 1) == t - 1) conv = i;
+    TORCH_CHECK(conv > 0, "extract_taps: tap ", t, " is not the ReLU behind one of the convolutions 1.. of this plan");
+    TORCH_CHECK(std::find(ordinals.begin(), ordinals.end(), conv) == ordinals.end(), "extract_taps: tap ", t, " named twice");
+    int pools = 0;  // a max pool follows convolution j where the next convolution starts two behind its ReLU
+    for (int j = 0; j < conv; ++j) pools += at_feature[j + 1] == at_feature[j] + (bn[j] ? 3 : 2) + 1;
+    int32_t cin = 0, cout = 0;
+    check(spr_vgg16_conv_shape(plan, conv, &cin, &cout), "extract_taps (plan)");
+    result.push_back(f32_like(a.images, a.n, cout, a.h >> pools, a.w >> pools));
+    ordinals.push_back(conv);
+    ptrs.push_back(a.n ? result.back().data_ptr<float>() : nullptr);
+  }
+  int32_t c = 0, oh = 0, ow = 0;
+  check(spr_vgg16_output_shape(plan, a.h, a.w, &c, &oh, &ow), "extract_taps (shape)");
+  at::Tensor out = f32_like(a.images, a.n, c, oh, ow);
+  if (a.n != 0) {
+    at::Tensor ws = at::empty({static_cast<int64_t>(std::max<size_t>(16, spr_vgg16_workspace_bytes(plan, a.n, a.h, a.w)))},
+                              a.images.options().dtype(at::kByte));
+    check(spr_vgg16_forward_taps(plan, a.images.data_ptr<uint8_t>(), a.n, a.h, a.w, a.ch, a.mean3, a.inv3, a.packed.data_ptr(),
+                                 ws.data_ptr(), out.data_ptr<float>(), static_cast<int32_t>(ordinals.size()), ordinals.data(),
+                                 ptrs.data(), current_stream(a.images)), "extract_taps");
+  }
+  result.push_back(out);
+  return result;
+}
+
+std::vector<at::Tensor> extract_taps(const at::Tensor& images, const at::Tensor& packed, int64_t arch, int64_t block,
+                                     std::vector<double> mean, std::vector<double> std_, int64_t compute, std::vector<int64_t> taps) {
+  check_device_tensor(images, "images");
+  check_device_tensor(packed, "packed");
+  TORCH_CHECK(images.scalar_type() == at::kByte && (images.dim() == 3 || (images.dim() == 4 && images.size(3) == 3)),
+              "images are uint8 [N, H, W] or [N, H, W, 3]");
+  TORCH_CHECK(mean.size() == 3 && std_.size() == 3, "mean and std hold three values");
+  const DeviceGuard guard(images.device());
+  const int device = images.device().index();
+  TapCall a{images, packed, {static_cast<float>(mean[0]), static_cast<float>(mean[1]), static_cast<float>(mean[2])},
+            {1.0f / static_cast<float>(std_[0]), 1.0f / static_cast<float>(std_[1]), 1.0f / static_cast<float>(std_[2])},
+            images.size(0), static_cast<int32_t>(images.size(1)), static_cast<int32_t>(images.size(2)), images.dim() == 4 ? 3 : 1};
+  if (arch >= 0 && arch <= 2) return vgg_taps(vgg_plan(device, arch, block, compute), block, a, taps);
+  const bool effnet = arch >= kArchEffnet && arch <= kArchEffnet + 8;
+  TORCH_CHECK(effnet || arch == kArchResnet || arch == kArchDensenet, "extract_taps: arch ", arch,
+              " (0 .. 2 plain VGG, 16 + EfficientNet arch, 32 ResNet50, 48 DenseNet_201)");
+  void* plan = nullptr;
+  {
+    std::lock_guard<std::mutex> lock(g_mutex);
+    const auto key = std::make_tuple(device, static_cast<int>(arch), static_cast<int>(block), static_cast<int>(compute));
+    auto it = g_backbone_plans.find(key);
+    if (it != g_backbone_plans.end()) {
+      plan = it->second;
+    } else {
+      const int32_t b = static_cast<int32_t>(block), ct = static_cast<int32_t>(compute);
+      if (effnet) {
+        spr_effnet_plan* p = nullptr;
+        check(spr_effnet_plan_create_ex(static_cast<int32_t>(arch - kArchEffnet), b, ct, &p), "extract_taps (plan)");
+        plan = p;
+      } else if (arch == kArchResnet) {
+        spr_resnet_plan* p = nullptr;
+        check(spr_resnet_plan_create_ex(b, ct, &p), "extract_taps (plan)");
+        plan = p;
+      } else {
+        spr_densenet_plan* p = nullptr;
+        check(spr_densenet_plan_create_ex(b, ct, &p), "extract_taps (plan)");
+        plan = p;
+      }
+      g_backbone_plans[key] = plan;
+    }
+  }
+  if (effnet) {
+    auto* p = static_cast<spr_effnet_plan*>(plan);
+    return backbone_taps(p, spr_effnet_packed_bytes(p), spr_effnet_output_shape, spr_effnet_tap_shape, spr_effnet_workspace_bytes,
+                         spr_effnet_forward_taps, a, taps);
+  }
+  if (arch == kArchResnet) {
+    auto* p = static_cast<spr_resnet_plan*>(plan);
+    return backbone_taps(p, spr_resnet_packed_bytes(p), spr_resnet_output_shape, spr_resnet_tap_shape, spr_resnet_workspace_bytes,
+                         spr_resnet_forward_taps, a, taps);
+  }
+  auto* p = static_cast<spr_densenet_plan*>(plan);
+  return backbone_taps(p, spr_densenet_packed_bytes(p), spr_densenet_output_shape, spr_densenet_tap_shape,
+                       spr_densenet_workspace_bytes, spr_densenet_forward_taps, a, taps);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(shoeprint_mi355x, m) {
+  m.def("extract_taps(Tensor images, Tensor packed, int arch, int block, float[] mean, float[] std, int compute, int[] taps) -> Tensor[]");
   m.def("ncc_scores(Tensor q, Tensor g, int crop=2, str method='auto', int max_prepared_bytes=0) -> Tensor");
   m.def("ranks(Tensor scores, Tensor match) -> Tensor");
   m.def("extract(Tensor images, Tensor packed, int arch, int block, float[] mean, float[] std, int compute=0) -> Tensor");
@@ -254,6 +403,7 @@ TORCH_LIBRARY_IMPL(shoeprint_mi355x, CompositeExplicitAutograd, m) {
   m.impl("ncc_scores", &ncc_scores);
   m.impl("ranks", &ranks);
   m.impl("extract", &extract);
+  m.impl("extract_taps", &extract_taps);
   m.impl("topk", &topk);
   m.impl("ncc_scores_located", &ncc_scores_located);
 }

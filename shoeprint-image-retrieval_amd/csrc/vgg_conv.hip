@@ -527,7 +527,7 @@ namespace {
 // a float32 NCHW copy of the unpooled result (tap, or null); c.out_nchw: the last stage's result
 int launch_conv16(int kind, const ConvCall& c, int pool, float* tap, hipStream_t s) {
   if (c.ks != 3 || c.stride != 1 || c.cin % kCk16 != 0 || c.cout % kTN != 0 || c.in_stride() != c.cin || c.out_stride() != c.cout ||
-      c.c_off != 0 || c.cout_real || c.res || c.in_scale || c.pre_s || c.pre_t || c.act > 1) {
+      c.c_off != 0 || c.cout_real || c.res || c.in_scale || c.pre_s || c.pre_t || c.act > 1 || c.tap_nchw) {
     set_error("launch_conv16_3x3: conv16_kernel is a plain 3 x 3 / stride 1 convolution with bias and ReLU (%d x %d / stride %d, "
               "%d -> %d channels)", c.ks, c.ks, c.stride, c.cin, c.cout);
     return SPR_ERR_UNSUPPORTED;

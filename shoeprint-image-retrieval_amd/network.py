@@ -56,6 +56,32 @@ _COMPUTE = {"float32": _lib.F32, "float16": _lib.F16, "bfloat16": _lib.BF16}
 _warned = False
 
 
+_VGG_CONVS_PER_STAGE = {"VGG16": (2, 2, 3, 3, 3), "VGG19": (2, 2, 4, 4, 4), "VGG19_BN": (2, 2, 4, 4, 4)}
+
+
+def tap_ends(model_type: str) -> list[int]:
+    """Every slice end into ``features`` (ResNet50: into its child list) at which ``Model.extract_taps_device`` can hand out
+    an activation, whatever the block; a model truncated at ``block`` takes those below it.  Plain VGGs: behind the ReLU of
+    every convolution but the first; EfficientNets: every stage end (not the stem alone, not the closing convolution, which
+    can only be the output); ResNet50: layer1, layer2; DenseNet_201: behind every dense block and transition."""
+    if model_type in _VGG_CONVS_PER_STAGE:
+        per_conv = 3 if model_type.endswith("_BN") else 2  # convolution [, BatchNorm], ReLU
+        ends, at = [], 0
+        for convs in _VGG_CONVS_PER_STAGE[model_type]:
+            for _ in range(convs):
+                at += per_conv
+                ends.append(at)
+            at += 1  # the max pool
+        return ends[1:]
+    if model_type in _RESNET_MODELS:
+        return [5, 6]
+    if model_type in _EFFNET_MODELS:
+        return list(range(2, 8 if model_type == "EfficientNetV2_S" else 9))
+    if model_type == "DenseNet_201":
+        return list(range(5, 12))
+    raise LookupError("Model string not found")
+
+
 def effnet_state_names(ops) -> list[tuple[str, str]]:
     """Module names of the layers in a torchvision efficientnet_v2 state dict, in ``Model.effnet_ops`` order: (convolution,
     BatchNorm) or, for a squeeze-excitation, (fc1, fc2).  Written from torchvision's module layout - features.0 = stem,
@@ -566,12 +592,15 @@ class Model:
         return out
 
     def extract_taps_device(self, images_dev, tap_features, in_channels: int = 1):
-        """One pass of the (plain VGG) extractor that also returns the activations at ``tap_features`` - slice ends into
-        ``model.features`` like ``block``, each just behind a ReLU (16 = conv3_3, 23 = conv4_3, 30 = conv5_3 for VGG16) -
-        as float32 device arrays [N, C_l, h_l, w_l], in that order; a tap equal to ``block`` is the network's output.
-        Multi-layer scoring (BASELINE config 5) feeds on this: the reference would run the extractor once per block."""
+        """One pass of the extractor that also returns the activations at ``tap_features`` - slice ends into
+        ``model.features`` like ``block`` (ResNet50: into [conv1, bn1, relu, maxpool, layer1, layer2, layer3]) - as float32
+        device arrays [N, C_l, h_l, w_l], in that order; a tap equal to ``block`` is the network's output.  Plain VGGs: each
+        tap just behind a ReLU (16 = conv3_3, 23 = conv4_3, 30 = conv5_3 for VGG16); EfficientNets: every stage end 2 ..
+        block - 1; ResNet50: 5, 6; DenseNet_201: 5 .. block - 1 (``accepted_taps``).  A tap is bit for bit the output of
+        the same model truncated there.  Multi-layer scoring (BASELINE config 5) feeds on this: the reference would run the
+        extractor once per block."""
         if not isinstance(self.family, _Vgg):
-            raise NotImplementedError("feature taps are built for the plain VGG backbones")
+            return self._extract_taps_c(images_dev, tap_features, in_channels)
         dev = self.dev
         n, h, w = dev.shape(images_dev)[:3]
         info = self.conv_info()          # (index in model.features, BatchNorm inside) per convolution
@@ -604,6 +633,48 @@ class Model:
             dev.ptr(out), nt, (C.c_int32 * max(1, nt))(*tap_convs), (C.c_void_p * max(1, nt))(*[dev.ptr(b) for b in tap_bufs]),
             dev.stream()))
         return taps
+
+    def accepted_taps(self) -> list[int]:
+        """The slice ends below ``block`` that ``extract_taps_device`` hands out (``block`` itself is always accepted)."""
+        return [t for t in tap_ends(self.model_str) if t < self.block]
+
+    def tap_shape(self, tap: int, in_h: int, in_w: int) -> tuple[int, int, int]:
+        """(C, h, w) of the activation at slice end ``tap`` (ResNet50, EfficientNet, DenseNet_201): spr_*_tap_shape."""
+        if tap == self.block:
+            return self.output_shape(in_h, in_w)
+        return self._ints(self.family.fn(self.lib, "tap_shape"), 3, tap, in_h, in_w)
+
+    def _extract_taps_c(self, images_dev, tap_features, in_channels: int, out=None, tap_out=None):
+        """``extract_taps_device`` of the families whose C entry point takes slice ends (spr_*_forward_taps).  ``out`` /
+        ``tap_out`` (a dict tap -> buffer): dense device float32 buffers to write into, as ``extract_device``'s ``out``."""
+        dev, fam = self.dev, self.family
+        n, h, w = dev.shape(images_dev)[:3]
+        want = [int(t) for t in tap_features]
+        inner = [t for t in want if t != self.block]
+        bad = [t for t in inner if t not in self.accepted_taps()]
+        if bad or len(set(inner)) != len(inner):
+            raise ValueError(f"taps {want}: {self.model_str}[:{self.block}] hands out the slice ends {self.accepted_taps()} "
+                             f"(each once) and its output ({self.block})")
+
+        def buffer(shape, given):
+            if given is None:
+                return dev.empty(shape, np.float32)
+            if tuple(dev.shape(given)) != shape:
+                raise ValueError(f"a buffer is {tuple(dev.shape(given))}, the features are {shape}")
+            _require_dense(given)
+            return given
+
+        out = buffer((n,) + tuple(self.output_shape(h, w)), out)
+        bufs = {t: buffer((n,) + tuple(self.tap_shape(t, h, w)), (tap_out or {}).get(t)) for t in inner}
+        ws = dev.empty_bytes(max(16, fam.fn(self.lib, "workspace_bytes")(self.handle, n, h, w)))
+        mean = (C.c_float * 3)(*self.mean)
+        inv_std = (C.c_float * 3)(*[np.float32(1.0) / np.float32(s) for s in self.std])
+        nt = len(inner)
+        self.lib.check(fam.fn(self.lib, "forward_taps")(
+            self.handle, dev.ptr(images_dev), n, h, w, in_channels, mean, inv_std, dev.ptr(self.packed), dev.ptr(ws),
+            dev.ptr(out), nt, (C.c_int32 * max(1, nt))(*inner), (C.c_void_p * max(1, nt))(*[dev.ptr(bufs[t]) for t in inner]),
+            dev.stream()))
+        return [out if t == self.block else bufs[t] for t in want]
 
     def _stage_pool(self, i: int) -> bool:
         """Does a max-pool follow convolution i (and its BatchNorm / ReLU) inside features[:block]?"""
@@ -675,17 +746,22 @@ class Model:
                     print(f"\rfeatures {done}/{len(images)}", end="" if done < len(images) else "\n", file=sys.stderr)
         return results
 
-    def get_multiple_feature_maps_device(self, images, progress: bool = True):
+    def get_multiple_feature_maps_device(self, images, progress: bool = True, taps=None):
         """``get_multiple_feature_maps`` that leaves the features in HBM: a ``features.FeatureSet`` whose ``to_host_list()``
         is that function's result, bit for bit.  ``images``: a host list as there, or ``features.DeviceImages`` (the loader's
         device-resident output: nothing is uploaded).  CLAHE and extraction run per image shape class in ``batch_size``
         pieces, each piece written straight into its slice of the feature class; image classes whose features share a shape
-        lie one behind the other in one feature class.  Nothing is copied to the host."""
+        lie one behind the other in one feature class.  Nothing is copied to the host.
+        ``taps``: slice ends as ``extract_taps_device`` takes them - then the result is a list of one ``FeatureSet`` per
+        tap, in that order, all out of ONE extractor pass per image batch; item order and shape classes of each set are
+        those of the single set (which the set of a tap equal to ``block`` is, bit for bit)."""
         from .features import DeviceImages, FeatureSet
 
         dev = self.dev
         if not isinstance(images, DeviceImages):
             images = DeviceImages.from_host(dev, images)
+        if taps is not None:
+            return self._tapped_feature_sets(images, [int(t) for t in taps], progress)
         total, done = len(images), 0
         # feature shape -> [(image class, first row in the feature class)], in order of first appearance
         layout: dict[tuple, list] = {}
@@ -708,6 +784,57 @@ class Model:
                         print(f"\rfeatures {done}/{total}", end="" if done < total else "\n", file=sys.stderr)
             classes.append((fshape, np.concatenate([images.classes[k][1] for k, _ in parts]), feats))
         return FeatureSet(dev, total, classes)
+
+    def _tapped_feature_sets(self, images, taps: list[int], progress: bool):
+        """``get_multiple_feature_maps_device`` with taps: per tap the layout of the single set (feature classes keyed by
+        that tap's shape, image classes of one feature shape one behind the other), filled by one tapped pass per batch."""
+        from .features import FeatureSet
+
+        dev = self.dev
+        vgg = isinstance(self.family, _Vgg)
+        total, done = len(images), 0
+        layouts, feats, where = [], [], []
+        for t in taps:
+            layout: dict[tuple, list] = {}
+            rows: dict[tuple, int] = {}
+            for k, (shape, idx, _) in enumerate(images.classes):
+                fshape = tuple(self._vgg_tap_shape(t, shape[0], shape[1]) if vgg else self.tap_shape(t, shape[0], shape[1]))
+                layout.setdefault(fshape, []).append((k, rows.get(fshape, 0)))
+                rows[fshape] = rows.get(fshape, 0) + len(idx)
+            layouts.append(layout)
+            feats.append({fshape: dev.empty((rows[fshape],) + fshape, np.float32) for fshape in layout})
+            where.append({k: (fshape, row0) for fshape, parts in layout.items() for k, row0 in parts})
+        for k, (shape, idx, batch) in enumerate(images.classes):
+            for start in range(0, len(idx), self.batch_size):
+                n = min(self.batch_size, len(idx) - start)
+                x = self.clahe_device(dev.narrow0(batch, start, n))
+                dst = [dev.narrow0(feats[j][where[j][k][0]], where[j][k][1] + start, n) for j in range(len(taps))]
+                in_channels = 3 if len(shape) == 3 else 1
+                if vgg:  # spr_vgg16_forward_taps names convolutions: its Python route allocates, the pieces are copied in
+                    index = dev.to_device(np.arange(n, dtype=np.int32))
+                    for src, d in zip(self.extract_taps_device(x, taps, in_channels), dst):
+                        self.lib.check(self.lib.spr_items_gather(dev.ptr(src), int(np.prod(dev.shape(src)[1:])), dev.ptr(index), n,
+                                                                 dev.ptr(d), _lib.F32, dev.stream()))
+                else:
+                    out = [d for t, d in zip(taps, dst) if t == self.block]
+                    self._extract_taps_c(x, taps, in_channels, out=out[0] if out else None,
+                                         tap_out={t: d for t, d in zip(taps, dst) if t != self.block})
+                done += n
+                if progress:
+                    print(f"\rfeatures {done}/{total}", end="" if done < total else "\n", file=sys.stderr)
+        return [FeatureSet(dev, total, [(fshape, np.concatenate([images.classes[k][1] for k, _ in parts]), feats[j][fshape])
+                                        for fshape, parts in layouts[j].items()]) for j in range(len(taps))]
+
+    def _vgg_tap_shape(self, tap: int, in_h: int, in_w: int) -> tuple[int, int, int]:
+        """Plain VGG: (C, h, w) of the activation at slice end ``tap`` (as ``extract_taps_device`` sizes its buffers)."""
+        if tap == self.block:
+            return self.output_shape(in_h, in_w)
+        info = self.conv_info()
+        ordinal = [i for i, (k, bn) in enumerate(info) if k + (2 if bn else 1) == tap - 1]
+        if not ordinal or ordinal[0] == 0:
+            raise ValueError(f"tap {tap}: not the ReLU behind one of the convolutions 1.. of features[:{self.block}]")
+        pools = sum(1 for j in range(ordinal[0]) if self._stage_pool(j))
+        return self.conv_shapes()[ordinal[0]][1], in_h >> pools, in_w >> pools
 
     def close(self):
         if getattr(self, "handle", None):

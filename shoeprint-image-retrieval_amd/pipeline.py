@@ -6,7 +6,9 @@ another block; the multi-layer score is build-defined (SURVEY "Mismatches": mean
 values, each of which is oracle-pinned).  Here
 
 * the extractor runs once per image batch and hands out the activations of every requested layer (``Model.
-  extract_taps_device`` -> ``spr_vgg16_forward_taps``);
+  extract_taps_device`` -> ``spr_vgg16_forward_taps`` for the plain VGGs, ``spr_effnet_forward_taps`` /
+  ``spr_resnet_forward_taps`` / ``spr_densenet_forward_taps`` for the other backbones: the block-end layers store the tap
+  beside what they store for the next layer);
 * gallery batch i+1 is extracted on the extractor stream while the prepare + score chains of batch i run, one stream per
   feature layer (they are independent until the fusion);
 * per-layer score blocks stay in HBM and are folded into the mean by ``spr_scores_fuse``; the only device-to-host copy is
@@ -23,7 +25,17 @@ VGG16_TAPS = {"conv3_3": 16, "conv4_3": 23, "conv5_3": 30}  # slice ends into vg
 
 
 class MultiLayerPipeline:
-    def __init__(self, model, scorer, taps=(16, 23, 30), batch_size: int = 64, clahe: bool = True):
+    """``model``: any ``network.Model``; ``taps``: the slice ends to score, the deepest being the model's block (``Model.
+    accepted_taps``).  The plain VGGs default to conv3_3 + conv4_3 + conv5_3; every other backbone names its taps, e.g.
+    ``MultiLayerPipeline(Model(cfg, 6), scorer, taps=(4, 6))`` for blocks 4 and 6 of EfficientNetV2_M."""
+
+    def __init__(self, model, scorer, taps=None, batch_size: int = 64, clahe: bool = True):
+        if taps is None:
+            if not str(getattr(model, "model_str", "VGG16")).startswith("VGG"):
+                raise ValueError(f"{model.model_str}: name the taps to score (slice ends {model.accepted_taps()} and the "
+                                 f"block, {model.block})")
+            taps = tuple(VGG16_TAPS.values())
+        taps = tuple(int(t) for t in taps)
         if model.block != max(taps):
             raise ValueError(f"the model must be truncated at the deepest tap ({max(taps)}), not {model.block}")
         self.model, self.scorer, self.taps = model, scorer, tuple(taps)

@@ -605,6 +605,29 @@ class NccScorer:
                                                     0.0 if k == 0 else 1.0, weight, self.dev.stream()))
         return out
 
+    def multi_layer_score_matrix_device(self, layer_sets, rotations=None, scales=None):
+        """The ragged, variant-aware sibling of ``multi_layer_scores_device``: ``layer_sets`` = [(query ``FeatureSet``,
+        gallery ``FeatureSet``), ...], one pair per feature layer of the same items (``Model.
+        get_multiple_feature_maps_device(taps=...)``; host lists are taken too).  Each layer's matrix is its
+        ``score_matrix_device`` - the maximum over the query variants of ``rotations`` x ``scales`` - and spr_scores_fuse
+        folds them into the device float32 [Q,G] mean.  Nothing leaves the device."""
+        layer_sets = list(layer_sets)
+        if not layer_sets:
+            raise ValueError("no feature layers given")
+        weight = 1.0 / len(layer_sets)
+        out = None
+        for k, (q, g) in enumerate(layer_sets):
+            layer_scores = self.score_matrix_device(q, g, rotations=rotations, scales=scales)
+            nq, ng = self.dev.shape(layer_scores)
+            if out is None:
+                out = self.dev.zeros((nq, ng), np.float32)
+            elif tuple(self.dev.shape(out)) != (nq, ng):
+                raise ValueError(f"layer {k} scores {nq} x {ng} items, the layers before it {tuple(self.dev.shape(out))}")
+            if nq * ng:
+                self.lib.check(self.lib.spr_scores_fuse(self.dev.ptr(out), self.dev.ptr(layer_scores), nq * ng,
+                                                        0.0 if k == 0 else 1.0, weight, self.dev.stream()))
+        return out
+
     def multi_layer_score_matrix(self, layers) -> np.ndarray:
         """Host copy of multi_layer_scores_device (one transfer, of the fused matrix)."""
         return self.dev.to_host(self.multi_layer_scores_device(layers))
