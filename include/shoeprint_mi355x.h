@@ -172,6 +172,30 @@ int spr_ncc_score_peaks(spr_ncc_plan* plan, const void* prepared_queries, int64_
                         int32_t* peak_tag, int64_t ld, int64_t col0, int accumulate_max, int32_t tag,
                         spr_stream_t stream);
 
+/* The list form of spr_ncc_score_peaks: a list of pairs instead of the whole n_queries x n_gallery grid (the second stage of
+ * a coarse-to-fine retrieval scores a few candidates per query on an expensive layer).  pairs: device int32 [n_pairs][2] of
+ * (position in prepared_queries, position in prepared_gallery); scores, peak_yx: device arrays of n_pairs entries, and so is
+ * peak_tag unless it is NULL.  It is a peak form always: lists are thousands of pairs, not millions.
+ *  - Entry p receives bit for bit what spr_ncc_score_peaks stores in cell (q, g) = pairs[p] for the same plan, prepared
+ *    buffers, accumulate_max, tag and previous entry: the score floored at 0, the first maximum in row-major order,
+ *    (0, -1, -1) where the score is 0, and the accumulate / tag rule written above.
+ *  - Pairs may repeat and come in any order; every entry has its own output, so no two workgroups write the same word.
+ *    (Neighbouring entries that name the same gallery item share its lines in L2: a caller that can sorts by g.)
+ *  - An entry whose q lies outside [0, n_queries) or whose g lies outside [0, n_gallery) is skipped: nothing is read for it
+ *    and its three outputs are left alone.  The list is device data the host cannot look at, so the kernels test every entry;
+ *    it is also how a caller pads a list.
+ *  - n_pairs == 0 is a no-op.  A NULL pointer (peak_tag excepted) or a negative size is SPR_ERR_ARG; n_queries and n_gallery
+ *    have the limits of spr_ncc_score.  Launches are sliced as the dense forms' are, so n_pairs has no limit of its own.
+ *  - spr_ncc_plan_has_list: 1 for SPR_NCC_FFT plans whose working set lies in LDS (every grid but the 384 x 192 workspace
+ *    instance) and for SPR_NCC_DIRECT plans; 0 for the workspace instance, whose kernel is a persistent team grid, and for
+ *    the matrix-core methods, whose workgroups score 64 queries per gallery item.  On those spr_ncc_score_list returns
+ *    SPR_ERR_UNSUPPORTED before anything is launched (score the block densely and gather the cells). */
+int spr_ncc_plan_has_list(const spr_ncc_plan* plan); /* 1 / 0 */
+int spr_ncc_score_list(spr_ncc_plan* plan, const void* prepared_queries, int64_t n_queries,
+                       const void* prepared_gallery, int64_t n_gallery, const int32_t* pairs, int64_t n_pairs,
+                       float* scores, int32_t* peak_yx, int32_t* peak_tag, int accumulate_max, int32_t tag,
+                       spr_stream_t stream);
+
 /* Debug / parity entry point (scripts/summed_feature_maps.py:1-6, similarity.py:100-104):
  * per-channel NCC maps of ONE prepared query against ONE prepared gallery item, float32
  * [C, g_h-2*crop, g_w-2*crop] (device). */

@@ -12,6 +12,9 @@ features and scores stay in device memory from the extractor to the ranks (featu
 and the shortlist come back, the printed output and the ranks are the same.  With ``[mi355x] fuse_blocks = [..]`` (default []: off)
 a cluster whose block is b is scored on the feature layers {t in fuse_blocks : t < b} and b - one tapped extractor pass, one score
 matrix per layer, their mean on the device (``fused_ranks``); not together with ``shortlist`` or ``gallery_cache``.
+With ``[mi355x] cascade_blocks = [..]`` (default []: off) such a cluster is ranked coarse to fine instead (``cascade_ranks``): the
+block b is scored against the whole gallery, its ``cascade_depth`` best prints per query are scored on the layers
+{t in cascade_blocks : t < b} as a list of pairs and re-ranked by the mean over all layers; ``shortlist`` lists the re-ranked prints.
 """
 
 import os
@@ -23,7 +26,8 @@ from shoeprint_image_retrieval_amd.dataloader import Dataloader
 from shoeprint_image_retrieval_amd.features import DeviceImages, FeatureSet
 from shoeprint_image_retrieval_amd.network import Model
 from shoeprint_image_retrieval_amd.parse_results import cmp_all, mean_average_precision, rank1
-from shoeprint_image_retrieval_amd.similarity import compare_maps, retrieve_resident, retrieve_with_scores, scorer_from_config
+from shoeprint_image_retrieval_amd.similarity import (compare_maps, retrieve_cascade, retrieve_resident, retrieve_with_scores,
+                                                      scorer_from_config)
 from shoeprint_image_retrieval_amd.variants import variant_labels
 
 
@@ -85,6 +89,32 @@ def fused_ranks(model, layers, shoemark_images, shoeprint_images, matching_shoep
     return ranks
 
 
+def cascade_ranks(model, layers, shoemark_images, shoeprint_images, matching_shoeprint_ids, config, gallery_files, k):
+    """[mi355x] cascade_blocks: one tapped extractor pass per image batch hands out the feature layers ``layers`` (slice ends,
+    the model's block last); the block is the coarse layer of ``retrieve_cascade``, the layers below it re-rank its
+    ``cascade_depth`` best prints per query.  Prints the rank line per query and, with ``k`` > 0, its k best prints by the
+    fused score, variant and offset from the finest layer."""
+    comp = config["comparison"]
+    scorer = scorer_from_config(config)
+    shoemark_sets = model.get_multiple_feature_maps_device(shoemark_images, taps=layers)
+    shoeprint_sets = model.get_multiple_feature_maps_device(shoeprint_images, taps=layers)
+    print("Calculating ranks:")
+    cascade = retrieve_cascade(list(zip(shoemark_sets, shoeprint_sets)), config, int(config["mi355x"]["cascade_depth"]), coarse=-1,
+                               scorer=scorer)
+    ranks = cascade.ranks(matching_shoeprint_ids)
+    labels = variant_labels(comp.get("rotations"), comp.get("scales"))
+    for i, r in enumerate(ranks):
+        print(f"Print {i} true match ranked {r}")
+        for p, g in enumerate(cascade.index[i, :k]):
+            if g < 0:
+                break
+            dy, dx = cascade.offset[i, p]
+            v = cascade.variant[i, p]
+            print(f"    {p + 1}. {gallery_files[g]}  score {cascade.score[i, p]:.4f}  {labels[v] if v >= 0 else 'no variant'}  "
+                  f"offset ({dy}, {dx})")
+    return ranks
+
+
 def main(config_file: str = "run.toml") -> list[int]:
     config = load_config(config_file)
     dataloader = Dataloader(config)
@@ -99,6 +129,16 @@ def main(config_file: str = "run.toml") -> list[int]:
             layers = sorted({t for t in fuse if t < block} | {block})
             print(f"Scoring the feature layers {layers} of features[:{block}].")
             ranks = fused_ranks(model, layers, shoemark_images, shoeprint_images, matching_shoeprint_ids, config)
+            cmp_all(list(ranks), total_shoeprints=len(dataloader.shoeprint_files), total_shoemarks=len(dataloader.shoemark_files))
+            all_ranks += [int(r) for r in ranks]
+            continue
+        fine = sorted({t for t in (config["mi355x"].get("cascade_blocks") or []) if t < block})
+        if fine:
+            depth = int(config["mi355x"]["cascade_depth"])
+            print(f"Cascade: features[:{block}] ranks the gallery, its {depth} best prints per query are re-ranked on the "
+                  f"feature layers {fine + [block]}.")
+            ranks = cascade_ranks(model, fine + [block], shoemark_images, shoeprint_images, matching_shoeprint_ids, config,
+                                  sorted(dataloader.shoeprint_files), int(config["mi355x"].get("shortlist", 0) or 0))
             cmp_all(list(ranks), total_shoeprints=len(dataloader.shoeprint_files), total_shoemarks=len(dataloader.shoemark_files))
             all_ranks += [int(r) for r in ranks]
             continue

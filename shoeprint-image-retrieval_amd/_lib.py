@@ -70,6 +70,8 @@ SIGNATURES = {
     "spr_ncc_plan_has_peaks": (C.c_int, [_VP]),
     "spr_ncc_plan_enable_peaks": (C.c_int, [_VP]),
     "spr_ncc_score_peaks": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _I64, _I64, C.c_int, _I32, _VP]),
+    "spr_ncc_plan_has_list": (C.c_int, [_VP]),
+    "spr_ncc_score_list": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, C.c_int, _I32, _VP]),
     "spr_rank_true_match": (C.c_int, [_VP, _I64, _I64, _I64, _VP, _VP, _VP]),
     "spr_rank_count_greater": (C.c_int, [_VP, _I64, _I64, _I64, _I64, _VP, _VP, _VP, _VP]),
     "spr_scores_fuse": (C.c_int, [_VP, _VP, _I64, C.c_float, C.c_float, _VP]),

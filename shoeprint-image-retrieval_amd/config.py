@@ -3,7 +3,7 @@
 The reference reads the file with the ``toml`` package; ``tomli`` (same TOML 1.0 grammar) is what
 this image ships.  As in the reference, ``rotations = ""`` / ``scales = ""`` mean "none"
 (config.py:60-63).  Reference files stay valid: keys under ``[mi355x]`` are build-only extras
-(``dtype``, ``ncc_method``, ``max_prepared_gib``, ``weights``, ``shortlist``, ``device_resize``, ``matrix_core_peaks``, ``device_resident`` ...) and all have defaults.
+(``dtype``, ``ncc_method``, ``max_prepared_gib``, ``weights``, ``shortlist``, ``device_resize``, ``matrix_core_peaks``, ``device_resident``, ``cascade_blocks`` ...) and all have defaults.
 """
 
 from __future__ import annotations
@@ -55,6 +55,8 @@ class Mi355xConfig(TypedDict, total=False):
     device_resident: bool  # images (with device_resize), features and scores stay in device memory from the loader to the ranks
     max_feature_gib: float  # with device_resident: a cluster whose query + gallery features exceed it takes the host route
     fuse_blocks: list[int]  # slice ends below a cluster's block whose score matrices are fused with the block's (mean); [] = off
+    cascade_blocks: list[int]  # slice ends below a cluster's block that re-rank the block's cascade_depth best prints; [] = off
+    cascade_depth: int  # 1 .. 256: candidates per query the cascade keeps from its coarse layer
 
 
 class Config(TypedDict, total=False):
@@ -68,7 +70,7 @@ MI355X_DEFAULTS: dict[str, Any] = {"dtype": "float32", "ncc_method": "auto", "ma
                                    "gallery_cache": "", "extractor_dtype": "float32", "f32_matrix_cores": False,
                                    "shortlist": 0, "device_resize": False, "max_decoded_gib": 8.0,
                                    "matrix_core_peaks": False, "device_resident": False, "max_feature_gib": 64.0,
-                                   "fuse_blocks": []}
+                                   "fuse_blocks": [], "cascade_blocks": [], "cascade_depth": 100}
 
 
 def normalise(raw: dict) -> Config:
@@ -96,17 +98,34 @@ def normalise(raw: dict) -> Config:
     fuse = extra["fuse_blocks"]
     if not isinstance(fuse, list) or any(isinstance(t, bool) or not isinstance(t, int) for t in fuse):
         raise ValueError(f"[mi355x].fuse_blocks = {fuse!r}: expected a list of integers ([] = off)")
-    if fuse:
+    cascade, depth = extra["cascade_blocks"], extra["cascade_depth"]
+    if not isinstance(cascade, list) or any(isinstance(t, bool) or not isinstance(t, int) for t in cascade):
+        raise ValueError(f"[mi355x].cascade_blocks = {cascade!r}: expected a list of integers ([] = off)")
+    if isinstance(depth, bool) or not isinstance(depth, int) or not 1 <= depth <= 256:
+        raise ValueError(f"[mi355x].cascade_depth = {depth!r}: expected an integer in [1, 256]")
+    for name, taps in (("fuse_blocks", fuse), ("cascade_blocks", cascade)):
+        if not taps:
+            continue
         from .network import tap_ends  # (the table of slice ends per backbone; nothing is loaded or built)
 
         try:
             accepted = tap_ends(str(raw.get("model", {}).get("type", "")))
         except LookupError:
             accepted = None  # (Model raises the reference's LookupError for the type itself)
-        bad = [t for t in fuse if accepted is not None and t not in accepted]
+        bad = [t for t in taps if accepted is not None and t not in accepted]
         if bad:
-            raise ValueError(f"[mi355x].fuse_blocks = {fuse!r}: {bad} are not feature taps of {raw['model']['type']} "
+            raise ValueError(f"[mi355x].{name} = {taps!r}: {bad} are not feature taps of {raw['model']['type']} "
                              f"(slice ends {accepted})")
+    if cascade:
+        if fuse:
+            raise ValueError("[mi355x].cascade_blocks with fuse_blocks: a cluster is either fused over the whole gallery or "
+                             "re-ranked on its best candidates")
+        if extra["gallery_cache"]:
+            raise ValueError("[mi355x].cascade_blocks with gallery_cache: cached galleries hold one layer")
+        if shortlist > depth:
+            raise ValueError(f"[mi355x].cascade_depth = {depth} with shortlist = {shortlist}: the cascade re-ranks cascade_depth "
+                             "candidates per query and has no more than those to list")
+    if fuse:
         if shortlist > 0:
             raise ValueError("[mi355x].fuse_blocks with shortlist > 0: located peaks are per layer, a shortlist on the fused "
                              "score is not built")

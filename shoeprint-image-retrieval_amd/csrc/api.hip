@@ -345,6 +345,33 @@ extern "C" int spr_ncc_score_peaks(spr_ncc_plan* plan, const void* pq, int64_t n
   return score_pairs(plan, c);
 }
 
+extern "C" int spr_ncc_plan_has_list(const spr_ncc_plan* plan) {
+  if (!plan) return 0;
+  return (plan->method == SPR_NCC_FFT && !plan->geom.big) || plan->method == SPR_NCC_DIRECT ? 1 : 0;
+}
+
+extern "C" int spr_ncc_score_list(spr_ncc_plan* plan, const void* pq, int64_t nq, const void* pg, int64_t ng,
+                                  const int32_t* pairs, int64_t n_pairs, float* scores, int32_t* peak_yx, int32_t* peak_tag,
+                                  int accumulate_max, int32_t tag, spr_stream_t stream) {
+  if (!plan) { set_error("spr_ncc_score_list: null plan"); return SPR_ERR_ARG; }
+  if (!spr_ncc_plan_has_list(plan)) {  // before anything is launched
+    set_error("spr_ncc_score_list: the workspace instance of the FFT method and the matrix-core methods have no list form "
+              "(spr_ncc_plan_has_list() == 0)");
+    return SPR_ERR_UNSUPPORTED;
+  }
+  if (nq < 0 || ng < 0 || n_pairs < 0) { set_error("spr_ncc_score_list: bad sizes"); return SPR_ERR_ARG; }
+  if (n_pairs == 0) return SPR_OK;
+  if (!pq || !pg || !pairs || !scores || !peak_yx) { set_error("spr_ncc_score_list: null pointer"); return SPR_ERR_ARG; }
+  if (nq > 65535 || ng > (1 << 24)) { set_error("spr_ncc_score_list: too many items in one call (chunk the gallery)"); return SPR_ERR_ARG; }
+  PairCall c{pq, nq, pg, ng, scores, n_pairs, 0, accumulate_max, nullptr, static_cast<hipStream_t>(stream)};
+  c.peak_yx = peak_yx;
+  c.peak_tag = peak_tag;
+  c.tag = tag;
+  c.pairs = pairs;
+  c.n_pairs = n_pairs;
+  return score_pairs(plan, c);
+}
+
 extern "C" int spr_ncc_maps(spr_ncc_plan* plan, const void* pq, const void* pg, float* maps_out, spr_stream_t stream) {
   if (!plan || !pq || !pg || !maps_out) { set_error("spr_ncc_maps: null pointer"); return SPR_ERR_ARG; }
   return score_pairs(plan, PairCall{pq, 1, pg, 1, nullptr, 1, 0, 0, maps_out, static_cast<hipStream_t>(stream)});

@@ -60,7 +60,10 @@ prep_direct_kernel(NccGeom g, int is_query, const void* __restrict__ maps, float
 }
 
 // grid = (n_gallery, n_queries).  PEAKS: the form behind spr_ncc_score_peaks, an instantiation of its own
-template <int SPT, bool PEAKS>
+// LIST: the form behind spr_ncc_score_list, a peak form on a 1-D grid: workgroup w takes entry col0 + w of a device list of
+// (query, gallery) positions.  The list rides in `maps_out`, its length in `ld`, and the item counts every entry is tested
+// against in g.nh / g.nw, FFT fields this method has no use for: the form has no parameters of its own.
+template <int SPT, bool PEAKS, bool LIST>
 __global__ void __launch_bounds__(kThreads)
 pair_direct_kernel(NccGeom g, const float* __restrict__ pq, size_t q_item_floats, const float* __restrict__ pg,
                    size_t g_item_floats, float* __restrict__ scores, long long ld, long long col0, int accumulate,
@@ -71,7 +74,17 @@ pair_direct_kernel(NccGeom g, const float* __restrict__ pq, size_t q_item_floats
   float* P = reinterpret_cast<float*>(lds + 64);
   float* T = reinterpret_cast<float*>(lds + t_off);
   const int tid = static_cast<int>(threadIdx.x);
-  const size_t gi = blockIdx.x, qi = blockIdx.y;
+  size_t gi = blockIdx.x, qi = blockIdx.y;
+  size_t list_at = 0;  // LIST: this workgroup's entry = where its three outputs go
+  if constexpr (LIST) {
+    list_at = static_cast<size_t>(col0) + blockIdx.x;
+    if (list_at >= static_cast<size_t>(ld)) return;
+    const int32_t* entry = reinterpret_cast<const int32_t*>(maps_out) + 2 * list_at;
+    const int q = uniform(entry[0]), gg = uniform(entry[1]);
+    if (q < 0 || q >= g.nh || gg < 0 || gg >= g.nw) return;  // names no item: skipped whole (uniform per workgroup)
+    qi = static_cast<size_t>(q);
+    gi = static_cast<size_t>(gg);
+  }
   const int cy = g.th / 2, cx = g.tw / 2;
   const int n_img = g.ih * g.iw, n_tpl = g.th * g.tw;
   const float* q_base = pq + qi * q_item_floats;
@@ -135,7 +148,7 @@ pair_direct_kernel(NccGeom g, const float* __restrict__ pq, size_t q_item_floats
         if (x < g.iw) {
           const float val = acc[j] * inv[sy[k] * g.iw + x];
           total[k][j] += val;
-          if (maps_out) maps_out[(static_cast<size_t>(c) * g.ih + sy[k]) * g.iw + x] = val;
+          if (!LIST && maps_out) maps_out[(static_cast<size_t>(c) * g.ih + sy[k]) * g.iw + x] = val;
         }
       }
     }
@@ -153,7 +166,7 @@ pair_direct_kernel(NccGeom g, const float* __restrict__ pq, size_t q_item_floats
     }
     block_peak(best, where, red);
     if (tid == 0)
-      store_peak(scores, peak_yx, peak_tag, qi * ld + col0 + gi, best / static_cast<float>(g.channels), where, tag, accumulate);
+      store_peak(scores, peak_yx, peak_tag, LIST ? list_at : qi * ld + col0 + gi, best / static_cast<float>(g.channels), where, tag, accumulate);
     return;
   }
   float best = -3.0e38f;
@@ -217,17 +230,34 @@ int launch_prep_direct(const NccGeom& g, const PlanScratch&, const PrepCall& c) 
   return check_launch("prep_direct_kernel");
 }
 
-template <int SPT, bool PEAKS>
+template <int SPT, bool PEAKS, bool LIST = false>
 static int launch_pair_direct_t(const NccGeom& g, const PlanScratch&, const PairCall& c) {
   const DirectLds l = direct_lds(g);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pair_direct_kernel<SPT, PEAKS>),
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pair_direct_kernel<SPT, PEAKS, LIST>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
   // grid = (gallery, query) workgroups; HIP refuses 2^32 work-items and more along x: slices of the gallery
   const size_t g_item_floats = prepared_gallery_item_bytes(g, SPR_NCC_DIRECT) / sizeof(float);
   const int64_t max_g = pair_tiles_per_launch(1, kThreads);
+  if constexpr (LIST) {  // one workgroup per entry, sliced like the gallery below
+    NccGeom gl = g;
+    gl.nh = static_cast<int>(c.nq);  // (see the kernel)
+    gl.nw = static_cast<int>(c.ng);
+    for (int64_t e0 = 0; e0 < c.n_pairs; e0 += max_g) {
+      const int64_t n = c.n_pairs - e0 < max_g ? c.n_pairs - e0 : max_g;
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_direct_kernel<SPT, PEAKS, LIST>), dim3(static_cast<unsigned>(n)), dim3(kThreads),
+                         l.total, c.stream, gl, static_cast<const float*>(c.pq),
+                         prepared_query_item_bytes(g, SPR_NCC_DIRECT) / sizeof(float), static_cast<const float*>(c.pg),
+                         g_item_floats, c.scores, static_cast<long long>(c.n_pairs), static_cast<long long>(e0), c.accumulate,
+                         reinterpret_cast<float*>(const_cast<int32_t*>(c.pairs)), l.pws, l.tws, static_cast<unsigned>(l.t_off),
+                         c.peak_yx, c.peak_tag, c.tag);
+      const int rc = check_launch("pair_direct_kernel (list)");
+      if (rc != SPR_OK) return rc;
+    }
+    return SPR_OK;
+  }
   for (int64_t g0 = 0; g0 < c.ng; g0 += max_g) {
     const int64_t n = c.ng - g0 < max_g ? c.ng - g0 : max_g;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_direct_kernel<SPT, PEAKS>), dim3(static_cast<unsigned>(n), static_cast<unsigned>(c.nq)),
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_direct_kernel<SPT, PEAKS, LIST>), dim3(static_cast<unsigned>(n), static_cast<unsigned>(c.nq)),
                        dim3(kThreads), l.total, c.stream, g, static_cast<const float*>(c.pq),
                        prepared_query_item_bytes(g, SPR_NCC_DIRECT) / sizeof(float),
                        static_cast<const float*>(c.pg) + static_cast<size_t>(g0) * g_item_floats, g_item_floats, c.scores,
@@ -240,6 +270,16 @@ static int launch_pair_direct_t(const NccGeom& g, const PlanScratch&, const Pair
 }
 
 int launch_pair_direct(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
+  if (c.pairs) {  // spr_ncc_score_list
+    if (c.n_pairs == 0) return SPR_OK;
+    switch (g.strips_per_thread) {
+      case 1: return launch_pair_direct_t<1, true, true>(g, s, c);
+      case 2: return launch_pair_direct_t<2, true, true>(g, s, c);
+      case 4: return launch_pair_direct_t<4, true, true>(g, s, c);
+      case 8: return launch_pair_direct_t<8, true, true>(g, s, c);
+      default: set_error("direct NCC: unsupported strips per thread %d", g.strips_per_thread); return SPR_ERR_UNSUPPORTED;
+    }
+  }
   if (c.nq == 0 || c.ng == 0) return SPR_OK;
   switch (g.strips_per_thread) {
     case 1: return c.peak_yx ? launch_pair_direct_t<1, true>(g, s, c) : launch_pair_direct_t<1, false>(g, s, c);

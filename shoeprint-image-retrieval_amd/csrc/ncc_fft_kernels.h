@@ -1,6 +1,7 @@
-// FFT-method NCC scorer (the fast path): kernels, launchers and the table of instances.  Included by the two translation
-// units that instantiate them - ncc_fft.hip (prep kernels, plain pair kernels, the public functions of the method) and
-// ncc_fft_peaks.hip (the pair kernels in their peak form, SPR_FFT_PEAKS_TU defined before the include).
+// FFT-method NCC scorer (the fast path): kernels, launchers and the table of instances.  Included by the three translation
+// units that instantiate them - ncc_fft.hip (prep kernels, plain pair kernels, the public functions of the method),
+// ncc_fft_peaks.hip (the pair kernels in their peak form, SPR_FFT_PEAKS_TU defined before the include) and ncc_fft_list.hip
+// (the peak form over a list of pairs, SPR_FFT_LIST_TU).
 //
 // Correlation theorem:  num = IFFT2( FFT2(I0z) . conj(FFT2(t^)) )  on an nh x nw grid large enough
 // that the 'same'-mode lags are free of circular aliasing (nh >= ih + max(th/2, th-1-th/2), same
@@ -318,12 +319,21 @@ struct PairArgs {
 // PEAKS: the form behind spr_ncc_score_peaks - the arg-max beside the max, in the epilogue only - is its own instantiation
 // (as a runtime branch it cost the plain form registers, spills and occupancy in most instances).  A translation unit
 // instantiates one form: ncc_fft_peaks.hip defines SPR_FFT_PEAKS_TU before it includes this file.
-#ifdef SPR_FFT_PEAKS_TU
+// LIST: the form behind spr_ncc_score_list (ncc_fft_list.hip defines SPR_FFT_LIST_TU) - a peak form whose workgroup takes
+// entry col0 + blockIdx.x of a device list of (query, gallery) positions instead of a cell of the tile mapping.  It has no
+// parameters of its own (see PairArgs::kernarg_pad): the list rides in `maps_out`, its length in `ld`, the launch's first
+// entry in `col0` - three parameters a list launch has no other use for.  LDS-mode instances only.
+#ifdef SPR_FFT_LIST_TU
+constexpr bool kListTu = true;
+#else
+constexpr bool kListTu = false;
+#endif
+#if defined(SPR_FFT_PEAKS_TU) || defined(SPR_FFT_LIST_TU)
 constexpr bool kPeaksTu = true;
 #else
 constexpr bool kPeaksTu = false;
 #endif
-template <class C, int RR, int KW, int PF, int RK, bool BIG, bool PEAKS>
+template <class C, int RR, int KW, int PF, int RK, bool BIG, bool PEAKS, bool LIST>
 __global__ void __launch_bounds__(C::NT, BIG ? 1 : ((C::NT == 64 && RK > 0) ? 4 : 2))
 pair_fft_kernel(PairArgs g, const unsigned char* __restrict__ pq, size_t q_item_bytes,
                 const unsigned char* __restrict__ pg, size_t g_item_bytes, float* __restrict__ scores,
@@ -434,6 +444,7 @@ pair_fft_kernel(PairArgs g, const unsigned char* __restrict__ pq, size_t q_item_
   }
   for (; epoch < epoch_end; ++epoch) {
   int qi, gi_item;
+  size_t list_at = 0;  // LIST: this workgroup's entry of the list = where its three outputs go
   if constexpr (BIG) {
     int strip = epoch / g.epochs_full;
     strip = strip < g.strips ? strip : g.strips - 1;
@@ -444,6 +455,15 @@ pair_fft_kernel(PairArgs g, const unsigned char* __restrict__ pq, size_t q_item_
     qi = q0 + static_cast<int>(p - static_cast<long long>(gi_item) * qn);
     if (gi_item >= ng) continue;  // ragged last epoch of a strip
     __syncthreads();  // the previous pair's epilogue (red, the LDS tables) is behind every wave before this pair's stores
+  } else if constexpr (LIST) {
+    // list mode: one entry per workgroup.  The list is device data nobody has checked: an entry that names no item of
+    // the two prepared buffers is skipped whole - nothing read, nothing stored
+    list_at = static_cast<size_t>(col0) + blockIdx.x;
+    if (list_at >= static_cast<size_t>(ld)) return;
+    const int32_t* entry = reinterpret_cast<const int32_t*>(maps_out) + 2 * list_at;
+    qi = uniform(entry[0]);  // (every lane reads the same words: the item pointers stay in scalar registers)
+    gi_item = uniform(entry[1]);
+    if (qi < 0 || qi >= nq || gi_item < 0 || gi_item >= ng) return;  // uniform per workgroup
   } else {
     const int tiles_g = ceil_div(ng, kTileG);
     const int tile = g.tile0 + static_cast<int>(blockIdx.x) / (kTileQ * kTileG);
@@ -633,7 +653,7 @@ pair_fft_kernel(PairArgs g, const unsigned char* __restrict__ pq, size_t q_item_
           acc[rr][e + 1] = fmaf(v.y, ivf[e + 1], acc[rr][e + 1]);
         }
       }
-      if (maps_out) {  // debug / parity output of the per-channel maps (spr_ncc_maps): one uniform branch
+      if (!LIST && maps_out) {  // debug / parity output of the per-channel maps (spr_ncc_maps): one uniform branch
 #pragma unroll
         for (int pp = 0; pp < GW::SPL; ++pp) {
 #pragma unroll
@@ -678,8 +698,8 @@ pair_fft_kernel(PairArgs g, const unsigned char* __restrict__ pq, size_t q_item_
     }
     block_peak<C::NT>(best, where, red);
     if (tid == 0)
-      store_peak(scores, peak_yx, peak_tag, static_cast<size_t>(qi) * ld + col0 + gi_item, best / static_cast<float>(g.channels),
-                 where, tag, g.accumulate);
+      store_peak(scores, peak_yx, peak_tag, LIST ? list_at : static_cast<size_t>(qi) * ld + col0 + gi_item,
+                 best / static_cast<float>(g.channels), where, tag, g.accumulate);
   } else {
   float best = 0.0f;
 #pragma unroll
@@ -846,15 +866,35 @@ int pair_launch(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
   a.channels = g.channels; a.nq = static_cast<int>(nq); a.ng = static_cast<int>(ng);
   a.ih = g.ih; a.iw = g.iw; a.r_rows = g.r_rows; a.r_stride = g.r_stride; a.rounds_r = g.rounds_r;
   a.inv_per_chan = g.inv_per_chan; a.accumulate = c.accumulate;
-  const void* kernel = reinterpret_cast<const void*>(pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu>);
+  const void* kernel = reinterpret_cast<const void*>(pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu, kListTu>);
   (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
+  if constexpr (kListTu) {
+    // list mode: one workgroup per entry, in slices of as many entries as a dense launch holds pairs; the list goes down in
+    // `maps_out`, its length in `ld`, the slice's first entry in `col0` (see the kernel)
+    static_assert(!BIG, "the list form has LDS-mode instances only");
+    const int64_t max_entries = pair_tiles_per_launch(kTileQ * kTileG, C::NT) * (kTileQ * kTileG);
+    for (int64_t e0 = 0; e0 < c.n_pairs; e0 += max_entries) {
+      const int64_t n = c.n_pairs - e0 < max_entries ? c.n_pairs - e0 : max_entries;
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu, kListTu>),
+                         dim3(static_cast<unsigned>(n)), dim3(C::NT), l.total, c.stream, a,
+                         static_cast<const unsigned char*>(c.pq), prepared_query_item_bytes(g, SPR_NCC_FFT),
+                         static_cast<const unsigned char*>(c.pg), prepared_gallery_item_bytes(g, SPR_NCC_FFT), c.scores,
+                         static_cast<long long>(c.n_pairs), static_cast<long long>(e0),
+                         reinterpret_cast<float*>(const_cast<int32_t*>(c.pairs)), s.tw_h, s.tw_w,
+                         static_cast<unsigned>(l.r_off), static_cast<unsigned>(l.xbuf_off), static_cast<unsigned>(l.nyq_off),
+                         static_cast<unsigned char*>(nullptr), l.slot_bytes, c.peak_yx, c.peak_tag, c.tag);
+      const int rc = check_launch("pair_fft_kernel (list)");
+      if (rc != SPR_OK) return rc;
+    }
+    return SPR_OK;
+  }
   unsigned grid = 0;
   // ---- workspace mode: a persistent grid that exactly fills the device, 8 teams of co-resident workgroups, one
   // workspace slot per resident workgroup (the only launch form of this mode) ----
   int per_cu = 0, cus = 0, dev = 0;
   if (BIG && hipGetDevice(&dev) == hipSuccess &&
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu>, C::NT, l.total) == hipSuccess &&
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu, kListTu>, C::NT, l.total) == hipSuccess &&
       per_cu > 0 && cus >= 8) {
     int team_size = cus / 8 * per_cu;
     const size_t slots = s.ws ? s.ws_bytes / l.slot_bytes : 0;
@@ -880,7 +920,7 @@ int pair_launch(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
       a.tile0 = static_cast<int>(t0);
       grid = static_cast<unsigned>(n * kTileQ * kTileG);
     }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu>), dim3(grid),
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu, kListTu>), dim3(grid),
                        dim3(C::NT), l.total, c.stream, a, static_cast<const unsigned char*>(c.pq),
                        prepared_query_item_bytes(g, SPR_NCC_FFT), static_cast<const unsigned char*>(c.pg),
                        prepared_gallery_item_bytes(g, SPR_NCC_FFT), c.scores,
@@ -911,8 +951,13 @@ int pair_tb(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
 // BIG_ONLY: a grid that fft_geometry never selects in LDS mode has no LDS-mode instances
 template <class C, int PFA, bool BIG_ONLY>
 int pair_t(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
+  if constexpr (kListTu) {  // the workspace instance walks a persistent team grid: it has no list form
+    if (g.big) { set_error("spr_ncc_score_list: the workspace instance (grid %dx%d) has no list form", C::NH, C::NW); return SPR_ERR_UNSUPPORTED; }
+  }
 #ifndef SPR_SAN_SUBSET  // (the sanitizer build of the CPU emulation compiles the LDS-mode kernels only)
-  if (g.big) return pair_tb<C, PFA, true>(g, s, c);
+  if constexpr (!kListTu) {
+    if (g.big) return pair_tb<C, PFA, true>(g, s, c);
+  }
 #endif
   if constexpr (BIG_ONLY) return no_lds_mode<C>();
   else return pair_tb<C, PFA, false>(g, s, c);

@@ -133,7 +133,8 @@ struct Six {
 // PEAKS: the form behind spr_ncc_score_peaks is its own instantiation - the kernel is register-tight, and the plain form
 // carries nothing of it.  Only the epilogue differs.  MAPS: the form behind spr_ncc_maps, likewise - its stores sit inside the
 // accumulation of the row pass, where even a not-taken branch per accumulator set cuts the scoring forms into basic blocks.
-template <class C, bool PEAKS, bool MAPS>
+// LIST: the form behind spr_ncc_score_list, a peak form whose two halves take two entries of a list of pairs ("which pairs").
+template <class C, bool PEAKS, bool MAPS, bool LIST>
 __global__ void __launch_bounds__(2 * C::NT, 3)
 pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_bytes,
              const unsigned char* __restrict__ pg, size_t g_item_bytes, float* __restrict__ scores, long long ld,
@@ -149,16 +150,41 @@ pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_by
   // at its own pace (the gallery item's lines are then in L2 for whichever pair comes second).  Workgroups are dealt
   // round-robin over the 8 XCDs: workgroup w of a 16 x 16 tile (w % 8 = XCD) takes a 16-query x 2-gallery sub-tile,
   // so a gallery item's 112 KB per channel has 16 readers on one L2.
+  // LIST (spr_ncc_score_list): the two halves take entries 2w and 2w + 1 of a device list of (query, gallery) positions,
+  // which rides in `maps_out` (length `ld`, first entry of the launch `col0`: no parameters of its own).  The two pairs need
+  // not share anything.  An entry past the end of the list, or one that names no item of the prepared buffers - nobody has
+  // checked the list -, idles its half the way an odd query count does: it redoes the other half's pair and stores nothing,
+  // so both halves reach every __syncthreads; a workgroup with no valid entry returns.
   constexpr int kWgPerTile = kTileQ6 * kTileG6 / 2;
   const int tile = g.tile0 + static_cast<int>(blockIdx.x) / kWgPerTile;
   const int within = static_cast<int>(blockIdx.x) % kWgPerTile;
   const int tq = tile / g.tiles_g, tg = tile - tq * g.tiles_g;
   const int half = uniform(static_cast<int>(threadIdx.x) >= NT ? 1 : 0);
+  int list_q = 0, list_g = 0;  // LIST: this half's pair, whether it stores, and its entry = where its three outputs go
+  bool list_live = false;
+  size_t list_at = 0;
+  if constexpr (LIST) {
+    const size_t first = static_cast<size_t>(col0) + 2 * static_cast<size_t>(blockIdx.x);
+    const int32_t* entry = reinterpret_cast<const int32_t*>(maps_out) + 2 * first;
+    const bool has_a = first < static_cast<size_t>(ld), has_b = first + 1 < static_cast<size_t>(ld);
+    const int qa = has_a ? uniform(entry[0]) : -1, ga = has_a ? uniform(entry[1]) : -1;
+    const int qb = has_b ? uniform(entry[2]) : -1, gb = has_b ? uniform(entry[3]) : -1;
+    const bool ok_a = qa >= 0 && qa < g.nq && ga >= 0 && ga < g.ng;
+    const bool ok_b = qb >= 0 && qb < g.nq && gb >= 0 && gb < g.ng;
+    if (!ok_a && !ok_b) return;  // uniform per workgroup
+    const bool take_b = half ? ok_b : !ok_a;
+    list_live = half ? ok_b : ok_a;
+    list_q = take_b ? qb : qa;
+    list_g = take_b ? gb : ga;
+    list_at = first + half;
+  }
+  // (the dense forms below are, statement for statement, what they were compiled from before the list form existed - a
+  // constant LIST folds away in the front end - and come out of the compiler instruction for instruction as they did)
   const int q_first = tq * kTileQ6 + 2 * (within >> 4);
-  const int gi_item = tg * kTileG6 + 2 * (within & 7) + ((within >> 3) & 1);
-  if (q_first >= g.nq || gi_item >= g.ng) return;  // uniform per workgroup
-  const bool live = q_first + half < g.nq;          // an odd query count: the last workgroup's second half idles
-  const int qi = live ? q_first + half : q_first;   // (it redoes the first half's pair and writes nothing)
+  const int gi_item = LIST ? list_g : tg * kTileG6 + 2 * (within & 7) + ((within >> 3) & 1);
+  if (!LIST && (q_first >= g.nq || gi_item >= g.ng)) return;  // uniform per workgroup
+  const bool live = LIST ? list_live : q_first + half < g.nq;  // an odd query count: the last workgroup's second half idles
+  const int qi = LIST ? list_q : (live ? q_first + half : q_first);  // (it redoes the first half's pair and writes nothing)
 
   unsigned char* lds = dyn_lds();
   unsigned char* hl = lds + half * S::kHalfBytes;
@@ -549,8 +575,8 @@ pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_by
       float b = red[0];
       int p = red_pos[0];
       for (int w = 1; w < S::WAVES; ++w) peak_take(b, p, red[w], red_pos[w]);
-      store_peak(scores, peak_yx, peak_tag, static_cast<size_t>(qi) * ld + col0 + gi_item, b / static_cast<float>(g.channels), p,
-                 tag, g.accumulate);
+      store_peak(scores, peak_yx, peak_tag, LIST ? list_at : static_cast<size_t>(qi) * ld + col0 + gi_item,
+                 b / static_cast<float>(g.channels), p, tag, g.accumulate);
     }
     return;
   }
@@ -589,7 +615,7 @@ size_t pair6_lds_bytes() { return Six<C6>::kLdsBytes; }
 int pair6_max_rows() { return C6::kRows6; }
 int pair6_max_cols() { return 64; }  // outputs x[2m], x[2m+1] for m < 32
 
-template <bool PEAKS, bool MAPS>
+template <bool PEAKS, bool MAPS, bool LIST = false>
 static int launch_pair6_t(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
   if (!s.six_ctab) { set_error("pair6_kernel: the plan has no pre-twist table"); return SPR_ERR_ARG; }
   using S = Six<C6>;
@@ -597,20 +623,39 @@ static int launch_pair6_t(const NccGeom& g, const PlanScratch& s, const PairCall
   a.channels = g.channels; a.nq = static_cast<int>(c.nq); a.ng = static_cast<int>(c.ng);
   a.ih = g.ih; a.iw = g.iw; a.inv_per_chan = g.inv_per_chan; a.accumulate = c.accumulate;
   a.tiles_g = ceil_div(static_cast<int>(c.ng), kTileG6);
+  if (LIST) a.tiles_g = 1;  // (the list form has no tiles; the kernel's dead tile arithmetic divides by it)
   a.q_flags_off = static_cast<unsigned>(sizeof(cf) * static_cast<size_t>(g.channels) * g.spec_per_chan);
   a.g_flags_off = static_cast<unsigned>(static_cast<size_t>(g.channels) * (sizeof(cf) * g.spec_per_chan + sizeof(float) * g.inv_per_chan));
   if (g.channels > 1024) { set_error("pair6_kernel: at most 1024 channels"); return SPR_ERR_UNSUPPORTED; }
   const size_t lds_bytes = S::kLdsBytes + 2 * sizeof(unsigned short) * static_cast<size_t>(g.channels);
   a.prio_mode = env_int("SPR_P6_PRIO", 2);
   const int64_t tiles = static_cast<int64_t>(ceil_div(static_cast<int>(c.nq), kTileQ6)) * a.tiles_g;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pair6_kernel<C6, PEAKS, MAPS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pair6_kernel<C6, PEAKS, MAPS, LIST>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             kLdsLimit);
   // HIP refuses grids of 2^32 work-items and more: launch in slices of pair tiles
   const int64_t max_tiles = pair_tiles_per_launch(kTileQ6 * kTileG6 / 2, 2 * C6::NT);
+  if constexpr (LIST) {
+    // list mode: two entries per workgroup, in slices of as many entries as a dense launch holds pairs (an even number, so
+    // every slice starts on a workgroup's first entry); the list rides in `maps_out`, its length in `ld`, the slice's first
+    // entry in `col0` (see the kernel)
+    const int64_t max_entries = max_tiles * (kTileQ6 * kTileG6);
+    for (int64_t e0 = 0; e0 < c.n_pairs; e0 += max_entries) {
+      const int64_t n = c.n_pairs - e0 < max_entries ? c.n_pairs - e0 : max_entries;
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(pair6_kernel<C6, PEAKS, MAPS, LIST>), dim3(static_cast<unsigned>((n + 1) / 2)), dim3(2 * C6::NT),
+                         lds_bytes, c.stream, a, static_cast<const unsigned char*>(c.pq),
+                         prepared_query_item_bytes(g, SPR_NCC_FFT), static_cast<const unsigned char*>(c.pg),
+                         prepared_gallery_item_bytes(g, SPR_NCC_FFT), c.scores, static_cast<long long>(c.n_pairs),
+                         static_cast<long long>(e0), reinterpret_cast<float*>(const_cast<int32_t*>(c.pairs)), s.tw_h, s.six_ctab,
+                         c.peak_yx, c.peak_tag, c.tag);
+      const int rc = check_launch("pair6_kernel (list)");
+      if (rc != SPR_OK) return rc;
+    }
+    return SPR_OK;
+  }
   for (int64_t t0 = 0; t0 < tiles; t0 += max_tiles) {
     const int64_t n = tiles - t0 < max_tiles ? tiles - t0 : max_tiles;
     a.tile0 = static_cast<int>(t0);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair6_kernel<C6, PEAKS, MAPS>), dim3(static_cast<unsigned>(n * (kTileQ6 * kTileG6 / 2))), dim3(2 * C6::NT),
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair6_kernel<C6, PEAKS, MAPS, LIST>), dim3(static_cast<unsigned>(n * (kTileQ6 * kTileG6 / 2))), dim3(2 * C6::NT),
                        lds_bytes, c.stream, a, static_cast<const unsigned char*>(c.pq),
                        prepared_query_item_bytes(g, SPR_NCC_FFT), static_cast<const unsigned char*>(c.pg),
                        prepared_gallery_item_bytes(g, SPR_NCC_FFT), c.scores, static_cast<long long>(c.ld),
@@ -622,6 +667,7 @@ static int launch_pair6_t(const NccGeom& g, const PlanScratch& s, const PairCall
 }
 
 int launch_pair6(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
+  if (c.pairs) return c.n_pairs == 0 ? SPR_OK : launch_pair6_t<true, false, true>(g, s, c);  // spr_ncc_score_list
   if (c.nq == 0 || c.ng == 0) return SPR_OK;
   if (c.peak_yx) return launch_pair6_t<true, false>(g, s, c);
   return c.maps_out ? launch_pair6_t<false, true>(g, s, c) : launch_pair6_t<false, false>(g, s, c);

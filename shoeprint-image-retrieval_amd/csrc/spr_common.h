@@ -78,6 +78,10 @@ struct PairCall {
   int32_t* peak_yx = nullptr;
   int32_t* peak_tag = nullptr;
   int32_t tag = 0;
+  // spr_ncc_score_list: device [n_pairs][2] of (position in pq, position in pg); scores / peak_yx / peak_tag then hold one
+  // entry per pair (ld and col0 mean nothing), nq and ng are what the kernels test every entry against.  Always with peak_yx.
+  const int32_t* pairs = nullptr;
+  int64_t n_pairs = 0;
 };
 struct PrepCall {
   bool is_query;
@@ -102,6 +106,7 @@ int launch_pair_direct(const NccGeom& g, const PlanScratch& s, const PairCall& c
 int launch_prep_fft(const NccGeom& g, const PlanScratch& s, const PrepCall& c);
 int launch_pair_fft(const NccGeom& g, const PlanScratch& s, const PairCall& c);
 int launch_pair_fft_peaks(const NccGeom& g, const PlanScratch& s, const PairCall& c);  // c.peak_yx set (ncc_fft_peaks.hip)
+int launch_pair_fft_list(const NccGeom& g, const PlanScratch& s, const PairCall& c);   // c.pairs set (ncc_fft_list.hip)
 int launch_pair6(const NccGeom& g, const PlanScratch& s, const PairCall& c);  // six-wave pair kernel (ncc_pair6.hip)
 bool prep6_covers(const NccGeom& g);  // gallery of a six-wave plan with corner windows (ncc_prep6.hip)
 int launch_prep6(const NccGeom& g, const PlanScratch& s, const PrepCall& c);

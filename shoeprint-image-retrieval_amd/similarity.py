@@ -67,6 +67,8 @@ class _Plan:
         self.gallery_item_bytes = lib.spr_ncc_gallery_bytes(handle, 1)
         # spr_ncc_score_peaks: FFT and direct plans, and matrix-core plans that were asked (enable_peaks)
         self.has_peaks = bool(lib.spr_ncc_plan_has_peaks(handle))
+        # spr_ncc_score_list: FFT plans whose working set lies in LDS, and direct plans
+        self.has_list = bool(lib.spr_ncc_plan_has_list(handle))
 
     def close(self):
         if self.handle:
@@ -226,6 +228,17 @@ class NccScorer:
                                                     self.dev.ptr(scores), self.dev.ptr(peaks),
                                                     None if tags is None else self.dev.ptr(tags), ld, col0,
                                                     1 if accumulate_max else 0, int(tag), self.dev.stream()))
+
+    def score_list_prepared(self, plan: _Plan, pq, nq: int, pg, ng: int, pairs, n_pairs: int, scores, peaks, tags=None,
+                            accumulate_max: bool = False, tag: int = 0):
+        """spr_ncc_score_list: ``score_prepared`` with ``peaks`` for the ``n_pairs`` entries of ``pairs`` (device int32
+        [n_pairs, 2]: position in ``pq``, position in ``pg``) instead of the whole grid; ``scores`` / ``peaks`` / ``tags``
+        (optional) are device vectors of one entry per pair.  An entry that names no item is skipped.  Plans without the
+        form (``plan.has_list``: the workspace instance, the matrix-core methods): SprError."""
+        self.lib.check(self.lib.spr_ncc_score_list(plan.handle, self.dev.ptr(pq), nq, self.dev.ptr(pg), ng,
+                                                   self.dev.ptr(pairs), n_pairs, self.dev.ptr(scores), self.dev.ptr(peaks),
+                                                   None if tags is None else self.dev.ptr(tags),
+                                                   1 if accumulate_max else 0, int(tag), self.dev.stream()))
 
     def gallery_chunk_items(self, plan: _Plan, n_gallery: int, share: int = 1) -> int:
         """Gallery items per prepared chunk; ``share`` = how many prepared forms of the chunk are alive at once (one per
@@ -436,6 +449,80 @@ class NccScorer:
                 best[rows], variant[rows], yx[rows] = score[better], number, pos[better]
                 t_hw[rows] = (vs[0] - 2 * self.crop, vs[1] - 2 * self.crop)
         return best, variant, yx, t_hw
+
+    def score_pairs(self, shoemark_maps, shoeprint_maps, pairs, rotations=None, scales=None):
+        """``score_matrix_located`` read at ``pairs`` = [(query index, gallery index), ...], bit for bit, without the matrix:
+        host ``(scores float32 [P], variant int32 [P], yx int32 [P,2], t_hw int32 [P,2])`` - the score floored at 0 and
+        maximised over the variant lists, the lowest variant number among equal scores, its peak and the cropped size of
+        its template; (0, -1, (-1, -1), (0, 0)) where no variant rises above 0.  The third consumer of ``_blocks``: only the
+        shape classes and gallery chunks that hold a listed pair are stacked, prepared and visited.  Per block the pairs go
+        up once as a device list sorted by gallery position (neighbouring workgroups then share a gallery item's lines)
+        and every variant is one spr_ncc_score_list call.  A block one of whose plans has no list form (``plan.has_list``)
+        is scored densely, as ``_walk_device`` scores it, and its listed cells are gathered (``cells_device``); where it has
+        no peak form either, variant and position come from the second pass of ``locate``, as in ``_fill_unfused``."""
+        dev = self.dev
+        q_items, g_items = _side(dev, shoemark_maps), _side(dev, shoeprint_maps)
+        pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        n = len(pairs)
+        scores = np.zeros(n, dtype=np.float32)
+        variant = np.full(n, -1, dtype=np.int32)
+        yx = np.full((n, 2), -1, dtype=np.int32)
+        t_hw = np.zeros((n, 2), dtype=np.int32)
+        if n == 0:
+            return scores, variant, yx, t_hw
+        if pairs.min() < 0 or pairs[:, 0].max() >= len(q_items) or pairs[:, 1].max() >= len(g_items):
+            raise IndexError("a pair names an item outside the query or gallery set")
+        q_used, g_used = (sorted({int(i) for i in pairs[:, side]}) for side in (0, 1))
+        unlocated = []  # entries of blocks without a peak form
+        for b in self._blocks(q_items, g_items, rotations, scales, q_used, g_used):
+            q_pos = np.full(len(q_items), -1, dtype=np.int64)
+            g_pos = np.full(len(g_items), -1, dtype=np.int64)
+            q_pos[b.q_idx] = np.arange(len(b.q_idx))
+            g_pos[b.g_idx] = np.arange(len(b.g_idx))
+            sel = np.flatnonzero((q_pos[pairs[:, 0]] >= 0) & (g_pos[pairs[:, 1]] >= 0))
+            if len(sel) == 0:
+                continue
+            self.last_chunk_items = b.chunk_items  # (read by the tests)
+            qs, gs = q_pos[pairs[sel, 0]], g_pos[pairs[sel, 1]]
+            order = np.argsort(gs, kind="stable")
+            sel, qs, gs = sel[order], qs[order], gs[order]
+            sizes = {number: (vs[0] - 2 * self.crop, vs[1] - 2 * self.crop) for number, vs, _ in b.variants}
+            nq_b, ng_b = len(b.q_idx), len(b.g_idx)
+            if all(b.plans[vs].has_list for _, vs, _ in b.variants):
+                listed = dev.to_device(np.ascontiguousarray(np.stack([qs, gs], axis=1), dtype=np.int32))
+                sub = dev.zeros((len(sel),), np.float32)
+                sub_yx = dev.to_device(np.full(len(sel), -1, dtype=np.int32))
+                sub_tag = dev.to_device(np.full(len(sel), -1, dtype=np.int32))
+                for number, vs, v in b.variants:
+                    plan = b.plans[vs]
+                    pg = b.prepared(vs)
+                    self.score_list_prepared(plan, self.prepare_queries(plan, v), nq_b, pg, ng_b, listed, len(sel), sub, sub_yx,
+                                             sub_tag, accumulate_max=True, tag=number)
+                got = (dev.to_host(sub), dev.to_host(sub_tag), dev.to_host(sub_yx))
+            else:  # the dense route of _walk_device for this block alone, read at the listed cells
+                fused = all(b.plans[vs].has_peaks for _, vs, _ in b.variants)
+                sub = dev.zeros((nq_b, ng_b), np.float32)
+                sub_yx = dev.to_device(np.full((nq_b, ng_b), -1, dtype=np.int32)) if fused else None
+                sub_tag = dev.to_device(np.full((nq_b, ng_b), -1, dtype=np.int32)) if fused else None
+                for number, vs, v in b.variants:
+                    plan = b.plans[vs]
+                    pg = b.prepared(vs)
+                    self.score_prepared(plan, self.prepare_queries(plan, v), nq_b, pg, ng_b, sub, ng_b, 0, accumulate_max=True,
+                                        peaks=sub_yx, tags=sub_tag, tag=number)
+                got = (self.cells_device(sub, ng_b, qs, gs).view(np.float32),
+                       self.cells_device(sub_tag, ng_b, qs, gs) if fused else np.full(len(sel), -1, dtype=np.int32),
+                       self.cells_device(sub_yx, ng_b, qs, gs) if fused else np.full(len(sel), -1, dtype=np.int32))
+                if not fused:
+                    unlocated.append(sel)
+            scores[sel], variant[sel], yx[sel] = got[0], got[1], _unpack_yx(got[2])
+            hit = got[1] >= 0
+            t_hw[sel[hit]] = np.array([sizes[int(number)] for number in got[1][hit]], dtype=np.int32).reshape(-1, 2)
+        if unlocated:
+            rest = np.concatenate(unlocated)
+            rest = rest[scores[rest] > 0]  # (as the fused form: no position where the floored score is 0)
+            if len(rest):
+                _, variant[rest], yx[rest], t_hw[rest] = self._locate(q_items, g_items, pairs[rest], rotations, scales)
+        return scores, variant, yx, t_hw
 
     def score_matrix(self, shoemark_maps, shoeprint_maps, accumulate_into=None, rotations=None,
                      scales=None) -> np.ndarray:
@@ -869,6 +956,116 @@ def _shortlist(scorer: NccScorer, shoemark_maps, shoeprint_maps, scores, k: int,
             return out
     put(qs, ps, *scorer._locate(shoemark_maps, shoeprint_maps, np.stack([qs, gs], axis=1), rotations, scales)[1:])
     return out
+
+
+@dataclass
+class Cascade:
+    """What ``retrieve_cascade`` returns: per query its ``depth`` = M best prints of the coarse layer, re-ranked by the fused
+    score of all layers.  Slot [q, p] is the candidate ranked p + 1; slots beyond the gallery size hold index -1 (score 0,
+    variant -1, peak_yx (-1, -1), offset (0, 0)), and so do the located fields of a candidate whose located layer scores 0."""
+
+    coarse: Any                  # device float32 [Q,G]: the coarse layer's score matrix
+    index: np.ndarray            # int32 [Q,M] gallery index, best first
+    score: np.ndarray            # float32 [Q,M] fused score: the mean over the layers, the bits of the full fused matrix's cell
+    variant: np.ndarray          # int32 [Q,M] best query variant on the located layer
+    peak_yx: np.ndarray          # int32 [Q,M,2] peak of that variant's NCC map, cropped gallery-map coordinates of that layer
+    offset: np.ndarray           # int32 [Q,M,2] top-left corner of the cropped variant template in the cropped gallery map
+    scorer: Any = None
+
+    def shortlist(self, k: int) -> Shortlist:
+        """The first ``k`` columns (1 <= k <= M) as ``retrieve`` lays them out."""
+        if not 1 <= int(k) <= self.index.shape[1]:
+            raise ValueError(f"k = {k}: the cascade holds {self.index.shape[1]} candidates per query")
+        k = int(k)
+        return Shortlist(self.index[:, :k].copy(), self.score[:, :k].copy(), self.variant[:, :k].copy(),
+                         self.peak_yx[:, :k].copy(), self.offset[:, :k].copy())
+
+    def ranks(self, matching_pairs: Sequence[int]) -> np.ndarray:
+        """int32 [Q]: the position of query q's match among its re-ranked candidates + 1 where it is one of them, otherwise
+        its rank in the coarse matrix (``ranks_of_device``), which is above M by construction.  A match index outside the
+        gallery raises the reference's IndexError."""
+        ranks = self.scorer.ranks_of_device(self.coarse, matching_pairs)
+        match = np.asarray(matching_pairs, dtype=np.int64)
+        for q in range(len(ranks)):
+            at = np.flatnonzero(self.index[q] == match[q])
+            if len(at):
+                ranks[q] = at[0] + 1
+        return ranks
+
+
+def retrieve_cascade(layer_sets, config: dict, depth: int, *, coarse: int = -1, locate_layer: int | None = None,
+                     scorer: NccScorer | None = None) -> Cascade:
+    """Coarse-to-fine retrieval over feature layers of the same items.  ``layer_sets`` = [(query set, gallery set), ...] as
+    ``multi_layer_score_matrix_device`` takes them.  Layer ``coarse`` - the cheap one - is scored against the whole gallery
+    (``score_matrix_device``); per query its M = ``depth`` best prints (``topk_device``: the ranker's order) are the
+    candidates; every other layer scores only those Q * M pairs (``score_pairs``: spr_ncc_score_list); the candidates' fused
+    score is the mean over all layers, folded by spr_scores_fuse in the order of ``layer_sets`` exactly as the full fused
+    matrix is, so a candidate's fused score has the bits of that matrix's cell; and the candidates are re-ranked by it
+    (``topk_device`` in its merging form: ties go to the larger gallery index).  With ``depth`` >= G the result is the
+    ranking of the full fused matrix; below that, a query whose match is no candidate keeps its coarse rank.
+    ``config["comparison"]`` supplies rotations and scales.  ``locate_layer`` (default: the first layer that is not the
+    coarse one, the finest) gives the located fields.  1 <= depth <= 256; at least two layers."""
+    layer_sets = list(layer_sets)
+    if len(layer_sets) < 2:
+        raise ValueError(f"a cascade needs at least two feature layers, got {len(layer_sets)}")
+    if isinstance(depth, bool) or int(depth) != depth or not 1 <= int(depth) <= 256:
+        raise ValueError(f"depth = {depth!r}: expected an integer in [1, 256]")
+    n_layers = len(layer_sets)
+    if not -n_layers <= coarse < n_layers:
+        raise ValueError(f"coarse = {coarse}: there are {n_layers} layers")
+    coarse %= n_layers
+    if locate_layer is None:
+        locate_layer = 0 if coarse != 0 else 1
+    if not -n_layers <= locate_layer < n_layers:
+        raise ValueError(f"locate_layer = {locate_layer}: there are {n_layers} layers")
+    locate_layer %= n_layers
+    comp = config["comparison"]
+    rotations, scales = comp.get("rotations"), comp.get("scales")
+    scorer = scorer or scorer_from_config(config)
+    dev, lib = scorer.dev, scorer.lib
+    m = min(int(depth), 256)
+    coarse_scores = scorer.score_matrix_device(*layer_sets[coarse], rotations=rotations, scales=scales)
+    nq, ng = dev.shape(coarse_scores)
+    for k, (q, g) in enumerate(layer_sets):
+        if (len(_side(dev, q)), len(_side(dev, g))) != (nq, ng):
+            raise ValueError(f"layer {k} holds {len(_side(dev, q))} x {len(_side(dev, g))} items, the coarse layer {nq} x {ng}")
+    out = Cascade(coarse_scores, np.full((nq, m), -1, np.int32), np.zeros((nq, m), np.float32), np.full((nq, m), -1, np.int32),
+                  np.full((nq, m, 2), -1, np.int32), np.zeros((nq, m, 2), np.int32), scorer)
+    if nq == 0:
+        return out
+    top_s, top_i = scorer.topk_device(coarse_scores, m)
+    candidates = dev.to_host(top_i).astype(np.int32, copy=True)
+    qs, ps = np.nonzero(candidates >= 0)
+    pairs = np.stack([qs, candidates[qs, ps]], axis=1)
+    weight = 1.0 / n_layers
+    fused = dev.zeros((nq, m), np.float32)
+    located = None
+    for k, (q, g) in enumerate(layer_sets):
+        if k == coarse:
+            layer = top_s
+        else:
+            got = scorer.score_pairs(q, g, pairs, rotations=rotations, scales=scales)
+            if k == locate_layer:
+                located = got
+            vec = np.zeros((nq, m), np.float32)
+            vec[qs, ps] = got[0]
+            layer = dev.to_device(vec)
+        lib.check(lib.spr_scores_fuse(dev.ptr(fused), dev.ptr(layer), nq * m, 0.0 if k == 0 else 1.0, weight, dev.stream()))
+    if located is None:  # (the coarse layer was asked to locate: its candidates' pairs, scored once more with positions)
+        located = scorer.score_pairs(*layer_sets[locate_layer], pairs, rotations=rotations, scales=scales)
+    top_s, top_i = scorer.topk_device(fused, m, col_index=dev.to_device(candidates))
+    out.score[...] = dev.to_host(top_s)
+    out.index[...] = dev.to_host(top_i)
+    # the located fields follow their candidates to the re-ranked positions
+    slot = np.full((nq, ng), -1, dtype=np.int64)
+    slot[qs, candidates[qs, ps]] = np.arange(len(qs))
+    rq, rp = np.nonzero(out.index >= 0)
+    src = slot[rq, out.index[rq, rp]]
+    _, variant, yx, t_hw = located
+    out.variant[rq, rp], out.peak_yx[rq, rp] = variant[src], yx[src]
+    out.offset[rq, rp] = np.where((variant[src] >= 0)[:, None], yx[src] - t_hw[src] // 2, 0)
+    return out
+
 
 def _pair_maps(scorer: NccScorer | None, template: np.ndarray, image: np.ndarray, crop: int | None) -> np.ndarray:
     """Host float32 [C, ih, iw] NCC maps of one [C, h, w] template over one [C, h', w'] image."""
