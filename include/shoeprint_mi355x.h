@@ -59,6 +59,9 @@ enum spr_status {
 };
 
 enum spr_dtype { SPR_F32 = 0, SPR_F16 = 1, SPR_BF16 = 2 };
+/* A COMPUTE type of the plain-VGG extractor plans (spr_vgg_plan_create_ex), not a storage type: float32 values split into
+ * hi + lo bfloat16, three bf16 matrix-core products per float32 product.  No spr_ncc_* call and no other backbone takes it. */
+enum { SPR_COMPUTE_BF16X3 = 3 };
 
 /* Which pair kernel scores a (query, gallery) pair. */
 enum spr_ncc_method {
@@ -356,7 +359,24 @@ int spr_vgg_plan_create(int32_t arch, int32_t block, spr_vgg16_plan** plan_out);
  * f32 accumulation on v_mfma_f32_16x16x32_{f16,bf16} (BASELINE configs 3 and 5 ask for reduced precision): the weights and
  * the activations BETWEEN layers (and the normalised image the first convolution reads) are rounded to that type (nearest even),
  * bias / ReLU / pool and the last layer's output stay f32; a plan that consists of the first convolution alone stays f32.  Every later call on the plan (packed bytes, pack, workspace, forward)
- * follows the plan's type; the float32 NCHW output and the argument lists do not change. */
+ * follows the plan's type; the float32 NCHW output and the argument lists do not change.
+ *
+ * SPR_COMPUTE_BF16X3: float32-grade arithmetic on the bf16 matrix cores (conv_x3_kernel).  The contract:
+ *   split(v), v float32:  hi = round_bf16(v) (nearest even), lo = round_bf16(v - float(hi)); the subtraction is exact in
+ *                         float32, and v^ = float(hi) + float(lo) is exact in float32 and equals v to <= 2^-16 |v|.
+ *   weights               of every convolution behind the first are split once by spr_vgg16_pack_weights; the bias stays
+ *                         float32; the first convolution keeps its float32 layout and its float32 fmaf arithmetic (K = 27).
+ *   every later conv      per 32-channel chunk and tap three v_mfma_f32_16x16x32_bf16 into the same float32 accumulators, in
+ *                         this order: a_hi w_hi, a_hi w_lo, a_lo w_hi (a_lo w_lo, <= 2^-16 |a||w|, is dropped); chunks
+ *                         ascending, the nine taps ascending inside a chunk.
+ *   epilogue              + bias, ReLU, the float32 NCHW feature tap, the fused 2x2 max pool; the last stage stores float32
+ *                         NCHW `out`, every other stage (the first convolution included) stores split(value).
+ *   stored activations    NHWC, 4 bytes per channel (packed bytes, workspace and trace sizes are the float32 plan's): per pixel
+ *                         and per chunk of 32 channels 64 uint16 words - the 32 hi bfloat16 bit patterns of channels
+ *                         32 k .. 32 k + 31, then their 32 lo patterns; word index of (pixel p, channel c, part) =
+ *                         (p * C / 32 + c / 32) * 64 + part * 32 + c % 32 with part 0 = hi, 1 = lo.
+ * A plan that is its first convolution alone runs in float32, as for the 16-bit types.  spr_resnet_plan_create_ex,
+ * spr_effnet_plan_create_ex and spr_densenet_plan_create_ex answer SPR_ERR_UNSUPPORTED to this type (null plan). */
 int spr_vgg_plan_create_ex(int32_t arch, int32_t block, int32_t compute, spr_vgg16_plan** plan_out);
 int spr_vgg_plan_compute(const spr_vgg16_plan* plan);
 /* For convolution conv_index: its position in model.features (state-dict key features.<k>.weight) and whether
@@ -405,6 +425,8 @@ int spr_vgg16_forward_taps(spr_vgg16_plan* plan, const uint8_t* images, int64_t 
  *   record i, 0 < i < last   what stage i stored, behind bias / ReLU / the fused 2x2 max pool: NHWC [n][h_i][w_i][cout_i] in
  *                            the plan's compute type (float32 for a float32 plan)
  *   the last record          the float32 NCHW output [n][C][h][w], i.e. `out`
+ * An SPR_COMPUTE_BF16X3 plan's records 0 .. last - 1 carry type code 3 and hold the stored words as they are: 4 bytes per
+ * channel in the hi / lo layout of spr_vgg_plan_create_ex.
  * A float32 plan that is its first convolution alone has that one NCHW record.  Refused with SPR_ERR_UNSUPPORTED by both
  * entry points: a 16-bit plan that consists of its first convolution alone (it runs in float32, see spr_vgg_plan_create_ex,
  * and stores no 16-bit record).  SPR_ERR_SHAPE: the image vanishes under the pools. */

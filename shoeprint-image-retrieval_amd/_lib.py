@@ -15,6 +15,7 @@ DEFAULT_PATH = os.path.join(_HERE, "libshoeprint_mi355x.so")
 
 SPR_OK = 0
 F32, F16, BF16 = 0, 1, 2
+BF16X3 = 3  # SPR_COMPUTE_BF16X3: a compute type of the plain-VGG extractor plans, not a storage type
 NCC_AUTO, NCC_FFT, NCC_DIRECT, NCC_FFT_POW2, NCC_MFMA, NCC_MFMA_F32 = 0, 1, 2, 3, 4, 5
 METHOD_NAMES = {NCC_AUTO: "auto", NCC_FFT: "fft", NCC_DIRECT: "direct", NCC_FFT_POW2: "fft_pow2", NCC_MFMA: "mfma",
                 NCC_MFMA_F32: "mfma_f32"}

@@ -111,7 +111,8 @@ struct TraceLayout {
   size_t total = 0;
   int64_t n = 0;
   void add(int h, int w, int c, int dtype, int nchw) {
-    const size_t bytes = static_cast<size_t>(n) * h * w * c * (dtype == SPR_F32 ? 4 : 2);
+    // (SPR_COMPUTE_BF16X3 records hold a hi and a lo bfloat16 word per channel: 4 bytes, as float32)
+    const size_t bytes = static_cast<size_t>(n) * h * w * c * (dtype == SPR_F16 || dtype == SPR_BF16 ? 2 : 4);
     recs.push_back(TraceRec{total, bytes, h, w, c, dtype, nchw});
     total += align_up(bytes, 256);
   }

@@ -268,6 +268,10 @@ extern "C" int spr_effnet_plan_compute(const spr_effnet_plan* plan) { return pla
 extern "C" int spr_effnet_plan_create_ex(int32_t arch, int32_t block, int32_t compute, spr_effnet_plan** plan_out) {
   if (!plan_out) { set_error("spr_effnet_plan_create: null pointer"); return SPR_ERR_ARG; }
   *plan_out = nullptr;
+  if (compute == SPR_COMPUTE_BF16X3) {
+    set_error("spr_effnet_plan_create_ex: SPR_COMPUTE_BF16X3 (bfloat16x3, the hi + lo split) is built for the plain-VGG plans only");
+    return SPR_ERR_UNSUPPORTED;
+  }
   if (compute != SPR_F32 && compute != SPR_F16 && compute != SPR_BF16) {
     set_error("spr_effnet_plan_create_ex: compute type %d (SPR_F32 | SPR_F16 | SPR_BF16)", compute);
     return SPR_ERR_ARG;

@@ -156,6 +156,14 @@ __host__ __device__ inline uint16_t round_bf16(float v) {
   c.u += 0x7fffu + ((c.u >> 16) & 1u);                    // ties to even
   return static_cast<uint16_t>(c.u >> 16);
 }
+// split(v) of the SPR_COMPUTE_BF16X3 extractor plans: hi = round_bf16(v), lo = round_bf16(v - float(hi)); the subtraction is
+// exact in float32 (the contract is in the header, spr_vgg_plan_create_ex)
+__host__ __device__ inline void split_bf16(float v, uint16_t& hi, uint16_t& lo) {
+  hi = round_bf16(v);
+  union { uint32_t u; float f; } h;
+  h.u = static_cast<uint32_t>(hi) << 16;
+  lo = round_bf16(v - h.f);
+}
 __device__ __forceinline__ uint16_t round_f16(float v) {
   union { _Float16 h; uint16_t u; } c;
   c.h = static_cast<_Float16>(v);  // v_cvt_f16_f32: round to nearest even

@@ -213,7 +213,8 @@ spr_vgg16_plan* vgg_plan(int device, int64_t arch, int64_t block, int64_t comput
 // features[:block] of a plain VGG (arch 0 VGG16, 1 VGG19, 2 VGG19_BN; network.py:121-139, :185-186) on a uint8 batch
 // [N,H,W] (grey, repeated over three planes: network.py:67) or [N,H,W,3]; `packed` = the weights as spr_vgg16_pack_weights
 // wrote them; mean / std as the reference's transforms take them (network.py:60-71); compute = spr_dtype of the plan
-// (spr_vgg_plan_create_ex: 0 the exact f32 matrix cores, 1 / 2 float16 / bfloat16 operands).  float32 [N,C,h,w] out.
+// (spr_vgg_plan_create_ex: 0 the exact f32 matrix cores, 1 / 2 float16 / bfloat16 operands, 3 SPR_COMPUTE_BF16X3: hi + lo
+// bfloat16 operands, three products per float32 product).  float32 [N,C,h,w] out.
 at::Tensor extract(const at::Tensor& images, const at::Tensor& packed, int64_t arch, int64_t block, std::vector<double> mean,
                    std::vector<double> std_, int64_t compute) {
   check_device_tensor(images, "images");

@@ -16,6 +16,9 @@
 //                                           channels works as long as A and B agree).
 // Arithmetic per image at 512x256 up to conv3_3: 48.77 GFLOP (SURVEY §8 a-E2); bound: fp32 MFMA 157 TFLOP/s.
 //
+// conv16_kernel / conv_x3_kernel: the same tile on the 16-bit matrix cores - 16-bit operands (SPR_F16 | SPR_BF16 plans), or
+// float32 operands as hi + lo bfloat16 and three products per step (SPR_COMPUTE_BF16X3 plans, float32-grade results).
+//
 // conv_first_kernel: conv1_1 has 3 input planes (K = 27, 0.9 % of the flops): plain FMA kernel that
 // also applies ToTensor / repeat(3) / Normalize (network.py:60-71) — x'_c = (u8/255 - mean_c) * inv_std_c,
 // zero padding AFTER normalisation.
@@ -42,7 +45,16 @@ constexpr int kCk16 = 32;       // 16-bit matrix cores: input channels per chunk
 // Compute types of a plan (spr_vgg_plan_create_ex): the f32 matrix cores (exact, the reference's arithmetic, network.py:235),
 // or 16-bit operands with f32 accumulation - weights and the activations BETWEEN layers rounded to float16 / bfloat16
 // (round to nearest even), bias / ReLU / pool and the last layer's output in f32.
-enum { kF32 = SPR_F32, kF16 = SPR_F16, kBF16 = SPR_BF16 };
+enum { kF32 = SPR_F32, kF16 = SPR_F16, kBF16 = SPR_BF16, kX3 = SPR_COMPUTE_BF16X3 };
+// kX3: float32 values as hi + lo bfloat16, three bf16 matrix-core products per float32 product (conv_x3_kernel; the arithmetic
+// contract is in the header, spr_vgg_plan_create_ex)
+__host__ __device__ inline bool is16(int compute) { return compute == kF16 || compute == kBF16; }
+// Output channels per workgroup of conv_x3_kernel.  32: the hi and lo images of the 18 x 18 x 32 patch and of the 9 x 32 x 32
+// filter slab take 78 336 bytes of LDS, two workgroups per CU.  With 64 (115 200 bytes, one workgroup per CU, a third fewer
+// LDS reads per MFMA) the headline extraction measured 9 % slower.
+constexpr int kTNx3 = 32;
+static_assert(kTNx3 == 64 || kTNx3 == 32, "conv_x3_kernel: 64 or 32 output channels per workgroup");
+constexpr size_t kX3LdsBytes = 2 * 64 * (kPatch * kPatch + 9 * kTNx3);  // hi and lo image of the patch and of the filter slab
 
 struct Stage {
   int cin, cout;
@@ -93,13 +105,37 @@ pack_weights16_kernel(const float* __restrict__ w, const float* __restrict__ b, 
   for (int i = blockIdx.x * kThreads + threadIdx.x; i < cout; i += gridDim.x * kThreads) packed[b_off + i] = b[i];
 }
 
+// SPR_COMPUTE_BF16X3 plans: the weights of the convolutions behind the first, split once into hi + lo bfloat16 (split_bf16), as
+// [cout/kTNx3][cin/32][part: hi, lo][tap][n:kTNx3][c:32] - the slab of one (output block, chunk) is its hi image, then its lo
+// image, each in conv16_kernel's row format; 4 bytes per weight, the float32 slot.  Bias stays f32.
+__global__ void __launch_bounds__(kThreads)
+pack_weights_x3_kernel(const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ packed, size_t w_off,
+                       size_t b_off, int cin, int cout) {
+  uint16_t* dst16 = reinterpret_cast<uint16_t*>(packed + w_off);
+  const size_t total = static_cast<size_t>(cout) * cin * 9;
+  for (size_t i = static_cast<size_t>(blockIdx.x) * kThreads + threadIdx.x; i < total;
+       i += static_cast<size_t>(gridDim.x) * kThreads) {
+    const int tap = static_cast<int>(i % 9);
+    const int c = static_cast<int>((i / 9) % cin);
+    const int n = static_cast<int>(i / (static_cast<size_t>(9) * cin));
+    const int cb = n / kTNx3, nn = n % kTNx3, cc = c / kCk16, ci = c % kCk16;
+    const size_t slab = (static_cast<size_t>(cb) * (cin / kCk16) + cc) * (2 * 9 * kTNx3 * kCk16);
+    const size_t at = slab + (static_cast<size_t>(tap) * kTNx3 + nn) * kCk16 + ci;
+    uint16_t hi, lo;
+    split_bf16(w[i], hi, lo);
+    dst16[at] = hi;
+    dst16[at + 9 * kTNx3 * kCk16] = lo;
+  }
+  for (int i = blockIdx.x * kThreads + threadIdx.x; i < cout; i += gridDim.x * kThreads) packed[b_off + i] = b[i];
+}
+
 // ---------------------------------------------------------------- conv1_1 (+ pre-processing)
 // grid = (tiles, n images); out NHWC [n][H][W][64] or NCHW when it is the last stage.
 __global__ void __launch_bounds__(kThreads)
 conv_first_kernel(const uint8_t* __restrict__ images, int H, int W, int in_channels, float m0, float m1, float m2,
                   float s0, float s1, float s2, const float* __restrict__ wts, const float* __restrict__ bias,
                   int relu, int nchw, float* __restrict__ out, int kind16) {
-  // kind16 != 0 (16-bit plans, not the last stage): the NHWC activation is stored rounded to float16 / bfloat16
+  // kind16 != 0 (16-bit plans, not the last stage): the NHWC activation is stored rounded to float16 / bfloat16; kX3: split
   // Lane = output channel (its 27 weights live in registers), wave = strips of 8 output pixels: a strip reads
   // its 3 x 10 x 3 input values with wave-uniform (broadcast) 16-byte LDS reads and does 216 FMAs on them, and a
   // pixel's 64 channels leave as one 256-byte store.
@@ -161,7 +197,13 @@ conv_first_kernel(const uint8_t* __restrict__ images, int H, int W, int in_chann
         const float r = relu ? fmaxf(acc[i], 0.0f) : acc[i];
         if (nchw) out[((img * 64 + n) * H + y) * static_cast<size_t>(W) + x] = r;
         else if (kind16 == 0) out[((img * H + y) * static_cast<size_t>(W) + x) * 64 + n] = r;
-        else reinterpret_cast<uint16_t*>(out)[((img * H + y) * static_cast<size_t>(W) + x) * 64 + n] =
+        else if (kind16 == kX3) {  // split(r): a pixel's two 32-channel chunks, each 32 hi words then 32 lo words
+          uint16_t* o = reinterpret_cast<uint16_t*>(out) + ((img * H + y) * static_cast<size_t>(W) + x) * 128 + (n >> 5) * 64 + (n & 31);
+          uint16_t hi, lo;
+          split_bf16(r, hi, lo);
+          o[0] = hi;
+          o[32] = lo;
+        } else reinterpret_cast<uint16_t*>(out)[((img * H + y) * static_cast<size_t>(W) + x) * 64 + n] =
                  kind16 == kF16 ? round_f16(r) : round_bf16(r);
       }
     }
@@ -508,6 +550,238 @@ conv16_kernel(const uint16_t* __restrict__ in, int H, int W, int cin, int cout, 
   }
 }
 
+// ---------------------------------------------------------------- 3x3 conv, float32-grade, on the bf16 matrix cores
+// SPR_COMPUTE_BF16X3: conv16_kernel's implicit GEMM with every operand held as TWO bfloat16 images, hi and lo (split_bf16), and
+// three MFMAs per (pixel block i, channel block j), in this order into the same float32 accumulators:
+//   a_hi w_hi,  a_hi w_lo,  a_lo w_hi        (a_lo w_lo <= 2^-16 |a||w| is dropped)
+// for every chunk of 32 input channels ascending and, inside it, every tap ascending.  Tile, waves, LDS row format and swizzle,
+// the request / commit prefetch and the staged epilogue are conv16_kernel's; a workgroup computes kTNx3 output channels.
+// in:  NHWC split records - per pixel and 32-channel chunk 32 hi words then 32 lo words (uint16), so a chunk's hi half and
+//      its lo half are each one 64-byte LDS row and a lane's 16-byte quarter of either is one MFMA operand;
+// wts: pack_weights_x3_kernel's; out: the same split records or, for the last layer, NCHW float32; tap: NCHW float32.
+__global__ void __launch_bounds__(kThreads, 2)
+conv_x3_kernel(const uint16_t* __restrict__ in, int H, int W, int cin, int cout, const uint16_t* __restrict__ wts,
+               const float* __restrict__ bias, int relu, int pool, int nchw, float* __restrict__ out, float* __restrict__ tap) {
+  constexpr int kJB = kTNx3 / 16;                    // blocks of 16 output channels per wave
+  constexpr int kPatchRows = kPatch * kPatch;        // LDS rows (16 dwords) of one patch image
+  constexpr int kSlabRows = 9 * kTNx3;               // ... of one filter image
+  unsigned char* lds = dyn_lds();
+  float* patch = reinterpret_cast<float*>(lds);      // [hi, lo][18*18][16 dwords]
+  float* wl = patch + 2 * kPatchRows * kCS;          // [hi, lo][9*kTNx3][16 dwords]
+  const int tiles_x = ceil_div(W, kTile);
+  const int ty = static_cast<int>(blockIdx.x) / tiles_x, tx = static_cast<int>(blockIdx.x) % tiles_x;
+  const int y0 = ty * kTile, x0 = tx * kTile;
+  const int cb = static_cast<int>(blockIdx.y);
+  const size_t img = blockIdx.z;
+  const int tid = static_cast<int>(threadIdx.x);
+  const int wave = tid >> 6, lane = tid & 63;
+  const int p = lane & 15, q = lane >> 4;
+  const int nchunks = cin / kCk16;
+
+  f32x4 acc[4][kJB];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < kJB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const uint16_t* in_img = in + img * static_cast<size_t>(H) * W * cin * 2;  // two words per channel
+  // a 16-byte piece: (patch pixel pp, part, quarter qq) - eight consecutive work-items read a pixel's 128-byte chunk record
+  constexpr int kPatchPieces = kPatchRows * 8, kFilterPieces = 2 * kSlabRows * 4;
+  constexpr int kPP = (kPatchPieces + kThreads - 1) / kThreads, kFP = kFilterPieces / kThreads;
+  static_assert(kFilterPieces % kThreads == 0, "filter slab pieces divide over the workgroup");
+  static_assert(kSlabRows % 16 == 0, "the lo filter image starts on a swizzle period");
+  u32x4 pre_p[kPP], pre_f[kFP];
+  // A patch piece outside the image is zero.  Its load goes to the nearest pixel inside instead of being skipped - no branch
+  // around any load - and bit k of `inside` (the same for every chunk) decides at commit time whether piece k is kept.
+  unsigned inside = 0;
+#pragma unroll
+  for (int k = 0; k < kPP; ++k) {
+    const int i = tid + k * kThreads;
+    const int pp = i >> 3;
+    const int y = y0 - 1 + pp / kPatch, x = x0 - 1 + pp % kPatch;
+    if (i < kPatchPieces && y >= 0 && y < H && x >= 0 && x < W) inside |= 1u << k;
+  }
+  auto request = [&](int cc) {
+    const int t0 = opaque(tid);  // the eleven 64-bit addresses are recomputed per chunk, not kept in registers
+#pragma unroll
+    for (int k = 0; k < kPP; ++k) {
+      const int i = t0 + k * kThreads;
+      const int pp = i >> 3, part = (i >> 2) & 1, qq = i & 3;
+      const int yy = y0 - 1 + pp / kPatch, xx = x0 - 1 + pp % kPatch;
+      const int y = yy < 0 ? 0 : yy > H - 1 ? H - 1 : yy, x = xx < 0 ? 0 : xx > W - 1 ? W - 1 : xx;
+      pre_p[k] = *reinterpret_cast<const u32x4*>(in_img + (static_cast<size_t>(y) * W + x) * cin * 2 + cc * (2 * kCk16) +
+                                                 part * kCk16 + qq * 8);
+    }
+    // the slab of this (output block, chunk): hi image then lo image, contiguous in the packed buffer
+    const uint16_t* wsrc = wts + (static_cast<size_t>(cb) * nchunks + cc) * (2 * kSlabRows * kCk16);
+#pragma unroll
+    for (int k = 0; k < kFP; ++k) {
+      const int i = t0 + k * kThreads;
+      pre_f[k] = *reinterpret_cast<const u32x4*>(wsrc + (i >> 2) * kCk16 + (i & 3) * 8);
+    }
+  };
+  auto commit = [&]() {
+#pragma unroll
+    for (int k = 0; k < kPP; ++k) {
+      const int i = tid + k * kThreads;
+      const int pp = i >> 3, part = (i >> 2) & 1, qq = i & 3;
+      if (i < kPatchPieces)
+        *reinterpret_cast<u32x4*>(patch + (part * kPatchRows + pp) * kCS + qoff(pp, qq)) =
+            ((inside >> k) & 1u) ? pre_p[k] : u32x4{0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int k = 0; k < kFP; ++k) {
+      const int i = tid + k * kThreads;  // row i >> 2 of the two images back to back: the swizzle of a row and of its lo twin agree
+      *reinterpret_cast<u32x4*>(wl + (i >> 2) * kCS + qoff(i >> 2, i & 3)) = pre_f[k];
+    }
+  };
+  request(0);
+  for (int cc = 0; cc < nchunks; ++cc) {
+    __syncthreads();  // the previous chunk's fragments are consumed
+    commit();
+    __syncthreads();
+    if (cc + 1 < nchunks) request(cc + 1);
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const int dy = t / 3, dx = t % 3;
+      u32x4 ah[4], al[4], bh[kJB], bl[kJB];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = (wave * 4 + i + dy) * kPatch + (p + dx);
+        ah[i] = *reinterpret_cast<const u32x4*>(patch + row * kCS + qoff(row, q));
+        al[i] = *reinterpret_cast<const u32x4*>(patch + (kPatchRows + row) * kCS + qoff(row, q));
+      }
+#pragma unroll
+      for (int j = 0; j < kJB; ++j) {
+        const int row = t * kTNx3 + j * 16 + p;
+        bh[j] = *reinterpret_cast<const u32x4*>(wl + row * kCS + qoff(row, q));
+        bl[j] = *reinterpret_cast<const u32x4*>(wl + (kSlabRows + row) * kCS + qoff(row, q));
+      }
+      // an accumulator takes hi hi, then hi lo, then lo hi; each term runs over all blocks so that consecutive MFMAs are independent
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < kJB; ++j) acc[i][j] = mfma_bf16_16x16x32(ah[i], bh[j], acc[i][j]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < kJB; ++j) acc[i][j] = mfma_bf16_16x16x32(ah[i], bl[j], acc[i][j]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < kJB; ++j) acc[i][j] = mfma_bf16_16x16x32(al[i], bh[j], acc[i][j]);
+    }
+  }
+
+  // ---- epilogue, conv16_kernel's: lane (q, p) owns pixels x0 + 4q + jj of rows y0 + 4 wave + i, channel cb*kTNx3 + 16j + p
+  const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
+  constexpr int kET = kTNx3 + 4;  // row stride (floats) of the staging tile
+  float* T = reinterpret_cast<float*>(lds);
+  static_assert(128 * kET * sizeof(float) <= kX3LdsBytes, "the staging tile fits the operand tiles");
+  auto activations = [&](int j, float (&v)[4][4]) {
+    const int ch = cb * kTNx3 + j * 16 + p;
+    const float bv = bias[ch];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        const float t = acc[i][j][jj] + bv;
+        v[i][jj] = relu ? fmaxf(t, 0.0f) : t;
+      }
+    if (tap) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const int y = y0 + 4 * wave + i, x = x0 + 4 * q + jj;
+          if (y < H && x < W) tap[((img * cout + ch) * H + y) * static_cast<size_t>(W) + x] = v[i][jj];
+        }
+    }
+  };
+  if (nchw) {  // the last layer: float32 NCHW, direct
+#pragma unroll
+    for (int j = 0; j < kJB; ++j) {
+      const int ch = cb * kTNx3 + j * 16 + p;
+      float v[4][4];
+      activations(j, v);
+      if (pool) {
+#pragma unroll
+        for (int i2 = 0; i2 < 2; ++i2)
+#pragma unroll
+          for (int j2 = 0; j2 < 2; ++j2) {
+            const float m = fmaxf(fmaxf(v[2 * i2][2 * j2], v[2 * i2][2 * j2 + 1]),
+                                  fmaxf(v[2 * i2 + 1][2 * j2], v[2 * i2 + 1][2 * j2 + 1]));
+            const int y = (y0 + 4 * wave) / 2 + i2, x = (x0 + 4 * q) / 2 + j2;
+            if (y < Ho && x < Wo) out[((img * cout + ch) * Ho + y) * static_cast<size_t>(Wo) + x] = m;
+          }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) {
+            const int y = y0 + 4 * wave + i, x = x0 + 4 * q + jj;
+            if (y < Ho && x < Wo) out[((img * cout + ch) * Ho + y) * static_cast<size_t>(Wo) + x] = v[i][jj];
+          }
+      }
+    }
+    return;
+  }
+  uint16_t* out16 = reinterpret_cast<uint16_t*>(out);
+#pragma unroll 1
+  for (int h = 0; h < 2; ++h) {  // tile rows 8h .. 8h + 7: the waves 2h and 2h + 1
+    __syncthreads();             // the operand tiles / the previous half are consumed
+    if ((wave >> 1) == h) {
+      const int lw = wave & 1;
+#pragma unroll
+      for (int j = 0; j < kJB; ++j) {
+        float v[4][4];
+        activations(j, v);
+        if (pool) {  // the half holds 4 x 8 pooled pixels
+#pragma unroll
+          for (int i2 = 0; i2 < 2; ++i2)
+#pragma unroll
+            for (int j2 = 0; j2 < 2; ++j2) {
+              const float m = fmaxf(fmaxf(v[2 * i2][2 * j2], v[2 * i2][2 * j2 + 1]),
+                                    fmaxf(v[2 * i2 + 1][2 * j2], v[2 * i2 + 1][2 * j2 + 1]));
+              T[((2 * lw + i2) * 8 + 2 * q + j2) * kET + j * 16 + p] = m;
+            }
+        } else {     // 8 x 16 pixels
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) T[((4 * lw + i) * 16 + 4 * q + jj) * kET + j * 16 + p] = v[i][jj];
+        }
+      }
+    }
+    __syncthreads();
+    // eight channels of one pixel per work-item and pass: their split record is a 16-byte hi piece and a 16-byte lo piece
+    const int rows = pool ? 32 : 128, tw = pool ? 8 : 16;
+    constexpr int kPieces = kTNx3 / 8;
+    for (int e = tid; e < rows * kPieces; e += kThreads) {
+      const int row = e / kPieces, piece = e % kPieces;
+      const int ly = row / tw, lx = row - ly * tw;
+      const int y = (pool ? y0 / 2 + 4 * h : y0 + 8 * h) + ly, x = (pool ? x0 / 2 : x0) + lx;
+      if (y >= Ho || x >= Wo) continue;
+      const float4 f0 = *reinterpret_cast<const float4*>(T + row * kET + piece * 8);
+      const float4 f1 = *reinterpret_cast<const float4*>(T + row * kET + piece * 8 + 4);
+      const float f[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
+      uint16_t hi[8], lo[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) split_bf16(f[k], hi[k], lo[k]);
+      u32x4 oh, ol;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        oh[k] = static_cast<uint32_t>(hi[2 * k]) | (static_cast<uint32_t>(hi[2 * k + 1]) << 16);
+        ol[k] = static_cast<uint32_t>(lo[2 * k]) | (static_cast<uint32_t>(lo[2 * k + 1]) << 16);
+      }
+      const int c0 = cb * kTNx3 + piece * 8;  // first of the eight channels: chunk c0 / 32, position c0 % 32 inside it
+      uint16_t* o = out16 + ((img * Ho + y) * static_cast<size_t>(Wo) + x) * cout * 2 + (c0 >> 5) * (2 * kCk16) + (c0 & 31);
+      *reinterpret_cast<u32x4*>(o) = oh;
+      *reinterpret_cast<u32x4*>(o + kCk16) = ol;
+    }
+  }
+}
+
 constexpr size_t kConvLds = sizeof(float) * (kPatch * kPatch * kCS + 9 * kTN * kCS);
 static_assert(kConvLds == kConvLdsBytes, "one LDS size");
 
@@ -542,13 +816,29 @@ int launch_conv16(int kind, const ConvCall& c, int pool, float* tap, hipStream_t
                      c.out_nchw ? c.out_nchw : static_cast<float*>(c.out), tap);
   return check_launch("conv16_kernel");
 }
+// conv_x3_kernel for the stages behind the first of an SPR_COMPUTE_BF16X3 plan; arguments as launch_conv16's
+int launch_conv_x3(const ConvCall& c, int pool, float* tap, hipStream_t s) {
+  if (c.cin % kCk16 != 0 || c.cout % kTN != 0) {
+    set_error("conv_x3_kernel: %d -> %d channels (multiples of 32 and 64)", c.cin, c.cout);
+    return SPR_ERR_UNSUPPORTED;
+  }
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            static_cast<int>(kX3LdsBytes));
+  const dim3 grid(static_cast<unsigned>(ceil_div(c.h, kTile) * ceil_div(c.w, kTile)), static_cast<unsigned>(c.cout / kTNx3),
+                  static_cast<unsigned>(c.n));
+  hipLaunchKernelGGL(conv_x3_kernel, grid, dim3(kThreads), kX3LdsBytes, s, static_cast<const uint16_t*>(c.in), c.h, c.w, c.cin,
+                     c.cout, static_cast<const uint16_t*>(c.wts), c.bias, c.act, pool, c.out_nchw ? 1 : 0,
+                     c.out_nchw ? c.out_nchw : static_cast<float*>(c.out), tap);
+  return check_launch("conv_x3_kernel");
+}
 }  // namespace
 int launch_conv16_3x3(int kind, const ConvCall& c, hipStream_t s) { return launch_conv16(kind, c, 0, nullptr, s); }
 }  // namespace spr
 
 struct spr_vgg16_plan {
   int block;
-  int compute;  // SPR_F32 (f32 matrix cores, exact) | SPR_F16 | SPR_BF16 (16-bit operands, f32 accumulation)
+  int compute;  // SPR_F32 (f32 matrix cores, exact) | SPR_F16 | SPR_BF16 (16-bit operands, f32 accumulation) |
+                // SPR_COMPUTE_BF16X3 (hi + lo bfloat16 operands, three products, f32 accumulation)
   std::vector<spr::Stage> stages;
   std::vector<int> feature_index;  // position of every convolution in model.features
   std::vector<int> bn_inside;      // 1: its BatchNorm2d lies inside features[:block] (folded by the host)
@@ -569,8 +859,8 @@ extern "C" int spr_vgg_plan_compute(const spr_vgg16_plan* plan) { return plan ? 
 extern "C" int spr_vgg_plan_create_ex(int32_t arch, int32_t block, int32_t compute, spr_vgg16_plan** plan_out) {
   if (!plan_out) { set_error("spr_vgg_plan_create: null pointer"); return SPR_ERR_ARG; }
   *plan_out = nullptr;
-  if (compute != SPR_F32 && compute != SPR_F16 && compute != SPR_BF16) {
-    set_error("spr_vgg_plan_create_ex: compute type %d (SPR_F32 | SPR_F16 | SPR_BF16)", compute);
+  if (compute != SPR_F32 && compute != SPR_F16 && compute != SPR_BF16 && compute != SPR_COMPUTE_BF16X3) {
+    set_error("spr_vgg_plan_create_ex: compute type %d (SPR_F32 | SPR_F16 | SPR_BF16 | SPR_COMPUTE_BF16X3)", compute);
     return SPR_ERR_ARG;
   }
   static const int cfg_d[] = {64, 64, -1, 128, 128, -1, 256, 256, 256, -1, 512, 512, 512, -1, 512, 512, 512, -1};
@@ -613,8 +903,9 @@ extern "C" int spr_vgg_plan_create_ex(int32_t arch, int32_t block, int32_t compu
     if (has_bn) ++j;
     s.relu = (j < block && ops[j].kind == 'R') ? 1 : 0;
     s.pool = (s.relu && j + 1 < block && ops[j + 1].kind == 'P') ? 1 : 0;
-    // (16-bit plans: two weights per float slot; the first convolution's 32 x 64 padded 16-bit matrix fits its f32 slab)
-    s.w_off = off; off += static_cast<size_t>(s.cout) * s.cin * 9 / ((compute != SPR_F32 && s.cin != 3) ? 2 : 1);
+    // (16-bit plans: two weights per float slot; the first convolution's 32 x 64 padded 16-bit matrix fits its f32 slab.
+    // SPR_COMPUTE_BF16X3: a hi and a lo word per weight, the float32 slot)
+    s.w_off = off; off += static_cast<size_t>(s.cout) * s.cin * 9 / ((is16(compute) && s.cin != 3) ? 2 : 1);
     s.b_off = off; off += static_cast<size_t>(s.cout);
     off = (off + 3) / 4 * 4;  // keep every slab 16-byte aligned
     plan->stages.push_back(s);
@@ -683,14 +974,18 @@ extern "C" int spr_vgg16_pack_weights(spr_vgg16_plan* plan, const float* const* 
     const Stage& s = plan->stages[i];
     if (!weights[i] || !biases[i]) { set_error("spr_vgg16_pack_weights: null parameter %zu", i); return SPR_ERR_ARG; }
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    if (i == 0 && plan->compute != SPR_F32 && plan->stages.size() > 1) {
+    if (i == 0 && is16(plan->compute) && plan->stages.size() > 1) {
       // 16-bit plans: the first convolution runs on the matrix cores too (K = 27 padded to 32), unless it is the whole plan
       const int rc0 = pack_stem16(plan->compute, 3, weights[i], biases[i], static_cast<float*>(packed), s.w_off, s.b_off, hs);
       if (rc0 != SPR_OK) return rc0;
       continue;
     }
     int rc;
-    if (i > 0 && plan->compute != SPR_F32) {
+    if (i > 0 && plan->compute == SPR_COMPUTE_BF16X3) {
+      hipLaunchKernelGGL(pack_weights_x3_kernel, dim3(256), dim3(kThreads), 0, hs, weights[i], biases[i],
+                         static_cast<float*>(packed), s.w_off, s.b_off, s.cin, s.cout);
+      rc = check_launch("pack_weights_x3_kernel");
+    } else if (i > 0 && plan->compute != SPR_F32) {
       rc = pack_conv16_3x3(plan->compute, weights[i], biases[i], static_cast<float*>(packed), s.w_off, s.b_off, s.cin, s.cout, hs);
     } else {
       hipLaunchKernelGGL(pack_weights_kernel, dim3(256), dim3(kThreads), 0, hs, weights[i],
@@ -718,11 +1013,12 @@ extern "C" size_t spr_vgg16_workspace_bytes(const spr_vgg16_plan* plan, int64_t 
     if (f > biggest) biggest = f;
     if (s.pool) { h /= 2; w /= 2; }
   }
-  return 2 * align_up(biggest * (plan->compute == SPR_F32 ? sizeof(float) : sizeof(uint16_t)), 256);
+  return 2 * align_up(biggest * (is16(plan->compute) ? sizeof(uint16_t) : sizeof(float)), 256);
 }
 
 // Trace records (spr_vgg16_trace_layout): what every stage stored, behind bias / ReLU / pool - NHWC in the plan's compute
-// type for the stem and every stage but the last, the float32 NCHW output for the last.
+// type for the stem and every stage but the last (SPR_COMPUTE_BF16X3: the split records as stored, 4 bytes per channel), the
+// float32 NCHW output for the last.
 static TraceLayout vgg_trace_layout(const spr_vgg16_plan* plan, int64_t n, int in_h, int in_w) {
   TraceLayout lay;
   lay.n = n;
@@ -736,10 +1032,10 @@ static TraceLayout vgg_trace_layout(const spr_vgg16_plan* plan, int64_t n, int i
   return lay;
 }
 
-// Every float32 plan traces; a 16-bit plan needs stages behind its first convolution.
+// Every float32 plan traces; a 16-bit or SPR_COMPUTE_BF16X3 plan needs stages behind its first convolution.
 static int vgg_trace_refusal(const spr_vgg16_plan* plan, const char* who) {
   if (plan->compute != SPR_F32 && plan->stages.size() < 2) {
-    set_error("%s: a plan that is its first convolution alone runs in float32 and stores no 16-bit record", who);
+    set_error("%s: a plan that is its first convolution alone runs in float32 and stores no 16-bit or split record", who);
     return SPR_ERR_UNSUPPORTED;
   }
   return SPR_OK;
@@ -787,7 +1083,7 @@ static int vgg_forward(spr_vgg16_plan* plan, const uint8_t* images, int64_t n, i
     for (int t = 0; t < n_taps; ++t)
       if (tap_convs[t] == static_cast<int>(i)) tap = tap_out[t];
     const unsigned tiles = static_cast<unsigned>(ceil_div(h, kTile) * ceil_div(w, kTile));
-    if (i == 0 && plan->compute != SPR_F32 && !last) {
+    if (i == 0 && is16(plan->compute) && !last) {
       const int rc = launch_stem16(plan->compute, 3, 1, images, n, h, w, in_channels, mean3, inv_std3,
                                    reinterpret_cast<const uint16_t*>(pk + st.w_off), pk + st.b_off, st.relu,
                                    reinterpret_cast<uint16_t*>(dst), s);
@@ -802,7 +1098,8 @@ static int vgg_forward(spr_vgg16_plan* plan, const uint8_t* images, int64_t n, i
       ConvCall k;
       k.ks = 3; k.n = n; k.h = h; k.w = w; k.cin = st.cin; k.cout = st.cout;
       k.in = cur; k.wts = pk + st.w_off; k.bias = pk + st.b_off; k.act = st.relu; k.out = dst; k.out_nchw = last ? out : nullptr;
-      const int rc = launch_conv16(plan->compute, k, st.pool, tap, s);
+      const int rc = plan->compute == SPR_COMPUTE_BF16X3 ? launch_conv_x3(k, st.pool, tap, s)
+                                                         : launch_conv16(plan->compute, k, st.pool, tap, s);
       if (rc != SPR_OK) return rc;
     } else {
       hipLaunchKernelGGL(conv_mfma_kernel, dim3(tiles, static_cast<unsigned>(st.cout / kTN), static_cast<unsigned>(n)),

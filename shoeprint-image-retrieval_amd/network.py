@@ -52,7 +52,7 @@ _EFFNET_MODELS = {"EfficientNetV2_S": (0, IMAGENET_MEAN, IMAGENET_STD, 1e-3), "E
                   "EfficientNet_B1": (3, IMAGENET_MEAN, IMAGENET_STD, 1e-5), "EfficientNet_B2": (4, IMAGENET_MEAN, IMAGENET_STD, 1e-5),
                   "EfficientNet_B3": (5, IMAGENET_MEAN, IMAGENET_STD, 1e-5), "EfficientNet_B4": (6, IMAGENET_MEAN, IMAGENET_STD, 1e-5),
                   "EfficientNet_B5": (7, IMAGENET_MEAN, IMAGENET_STD, 1e-3), "EfficientNet_B7": (8, IMAGENET_MEAN, IMAGENET_STD, 1e-3)}
-_COMPUTE = {"float32": _lib.F32, "float16": _lib.F16, "bfloat16": _lib.BF16}
+_COMPUTE = {"float32": _lib.F32, "float16": _lib.F16, "bfloat16": _lib.BF16, "bfloat16x3": _lib.BF16X3}
 _warned = False
 
 
@@ -205,6 +205,7 @@ class _Family:
     lister = ""          # the Model method that lists the layers
     seeder = None        # synth.*_parameters(seed, layers)
     half = True          # float16 / bfloat16 plans exist
+    split = False        # bfloat16x3 plans exist (float32 values as hi + lo bfloat16 on the bf16 matrix cores)
     custom_op = False    # also served by the registered torch custom op (keyed by arch)
 
     def __init__(self, arch, mean, std, bn_eps=BN_EPS):
@@ -240,7 +241,7 @@ class _Family:
 
 class _Vgg(_Family):
     """Layers: (cin, cout, index in model.features, BatchNorm2d inside the truncation)."""
-    prefix, count, custom_op = "vgg16", "num_convs", True
+    prefix, count, custom_op, split = "vgg16", "num_convs", True, True
 
     def create(self, m, handle):
         return m.lib.spr_vgg_plan_create_ex(self.arch, m.block, _COMPUTE[m.compute], handle)
@@ -491,9 +492,14 @@ class Model:
         self.dev = device
         # [mi355x].extractor_dtype: compute type of the convolutions behind the first layer ("float32": the f32 matrix cores,
         # exact, the reference's arithmetic; "bfloat16" / "float16": 16-bit operands, f32 accumulation - BASELINE configs 3 / 5)
+        # "bfloat16x3" (plain VGGs): float32 weights and activations split into hi + lo bfloat16, three bf16 matrix-core
+        # products per float32 product - the float32 plan's accuracy class and data flow (SPR_COMPUTE_BF16X3)
         self.compute = str((config.get("mi355x") or {}).get("extractor_dtype", "float32") or "float32")
         if self.compute not in _COMPUTE:
             raise ValueError(f"[mi355x].extractor_dtype = {self.compute!r}: expected one of {sorted(_COMPUTE)}")
+        if self.compute == "bfloat16x3" and not fam.split:
+            raise NotImplementedError(f"{self.model_str}: extractor_dtype = \"bfloat16x3\" is built for VGG16 / VGG19 / VGG19_BN; "
+                                      "use \"float32\" (or a 16-bit type)")
         if self.compute != "float32" and not fam.half:
             raise NotImplementedError(f"{self.model_str}: this backbone has no 16-bit matrix-core path; "
                                       "use [mi355x].extractor_dtype = \"float32\"")
