@@ -199,6 +199,31 @@ int spr_ncc_score_list(spr_ncc_plan* plan, const void* prepared_queries, int64_t
                        float* scores, int32_t* peak_yx, int32_t* peak_tag, int accumulate_max, int32_t tag,
                        spr_stream_t stream);
 
+/* The list form that also stores every pair's correlation surface: the channel-mean NCC map an examiner judges a peak by
+ * (is it sharp and alone, or one ripple of a periodic tread pattern; is a second alignment almost as good).  The pair kernels
+ * hold the finished map in registers in their epilogue; this form stores it instead of discarding it.  surfaces: device
+ * float32 [n_pairs][ih][iw], ih x iw = (g_h - 2 crop) x (g_w - 2 crop), the map shape of spr_ncc_maps; it does not depend on
+ * the template ('same' mode), so one buffer serves all variants of a query.
+ *  - scores, peak_yx, peak_tag receive bit for bit what spr_ncc_score_list stores for the same arguments and previous entries.
+ *  - surfaces[p][y][x] = acc(y, x) / (float)channels, where acc is the kernel's own float32 channel sum - the value the
+ *    arg-max is taken on -, not floored; the division is the float32 division that gives the score.  Hence
+ *    max(max over the surface, 0) has the bits of the entry's new score, and where the score is positive the surface at
+ *    peak_yx holds its maximum.  (The peak need not be the FIRST row-major arg-max of the surface: two sums may round to one
+ *    quotient.)
+ *  - accumulate_max == 0: the surface of every live entry is written, all ih * iw pixels, also where the score is 0.
+ *  - accumulate_max != 0: the surface is written if and only if this call replaces the entry's (score, peak, tag) by the rule
+ *    written above spr_ncc_score_peaks; otherwise all of it is left alone.  After a walk over variants the buffer holds the
+ *    winning variant's map.
+ *  - An entry that names no item is skipped: its four outputs are untouched.  Pairs may repeat.  n_pairs == 0 is a no-op.
+ *  - A NULL surfaces is SPR_ERR_ARG; the other argument checks, the limits and the launch slicing are spr_ncc_score_list's.
+ *  - spr_ncc_plan_has_surfaces: 1 exactly where spr_ncc_plan_has_list is 1.  On the workspace instance and the matrix-core
+ *    methods the call returns SPR_ERR_UNSUPPORTED before anything is launched (take spr_ncc_maps + spr_maps_mean there). */
+int spr_ncc_plan_has_surfaces(const spr_ncc_plan* plan); /* 1 / 0 */
+int spr_ncc_score_surfaces(spr_ncc_plan* plan, const void* prepared_queries, int64_t n_queries,
+                           const void* prepared_gallery, int64_t n_gallery, const int32_t* pairs, int64_t n_pairs,
+                           float* scores, int32_t* peak_yx, int32_t* peak_tag, float* surfaces, int accumulate_max,
+                           int32_t tag, spr_stream_t stream);
+
 /* Debug / parity entry point (scripts/summed_feature_maps.py:1-6, similarity.py:100-104):
  * per-channel NCC maps of ONE prepared query against ONE prepared gallery item, float32
  * [C, g_h-2*crop, g_w-2*crop] (device). */
@@ -249,6 +274,26 @@ int spr_topk_rows(const float* scores, int64_t ld, int64_t n_queries, int64_t n_
  * channels, h, w >= 1, else SPR_ERR_ARG; n_pairs == 0 is a no-op. */
 int spr_maps_peak(const float* maps, int64_t n_pairs, int32_t channels, int32_t h, int32_t w, float* out_score,
                   int32_t* out_yx, spr_stream_t stream);
+
+/* spr_maps_mean: the channel-mean map of every pair, for plans without a surfaces form.  maps as for spr_maps_peak;
+ * out: device float32 [n_pairs, h, w], out[p][y][x] = (float)(acc(y, x) / channels) with spr_maps_peak's float64 acc
+ * (sequential over c, starting from 0.0), so the maximum of out[p] has the bits of spr_maps_peak's out_score[p].
+ * channels, h, w >= 1, else SPR_ERR_ARG; n_pairs == 0 is a no-op. */
+int spr_maps_mean(const float* maps, int64_t n_pairs, int32_t channels, int32_t h, int32_t w, float* out,
+                  spr_stream_t stream);
+
+/* spr_surface_peaks: the n_peaks best separated peaks of every surface and the peak-to-sidelobe ratio of the first.
+ * surfaces: device float32 [n, h, w] (spr_ncc_score_surfaces, spr_maps_mean; finite values).  out_value: device float32
+ * [n, n_peaks]; out_yx: device int32 [n, n_peaks], positions packed as (y << 16) | x; out_psr: device float32 [n] or NULL.
+ *  - Peak 0 is the maximum: the larger value, among equal values the first in row-major order; its sign does not matter.
+ *  - Peak j is the same maximum over the pixels outside every window |y - y_i| <= ry && |x - x_i| <= rx of the peaks i < j.
+ *    Slots for which no pixel is left hold value 0 and position -1.  Values and positions are exact.
+ *  - out_psr = (float)((v0 - mu) / sigma), mu and sigma^2 the mean and the population variance of the pixels outside peak
+ *    0's window, accumulated in float64 in two passes (mu, then the sum of (v - mu)^2); 0 when fewer than two such pixels
+ *    exist or sigma is 0.
+ *  - SPR_ERR_ARG unless 1 <= n_peaks <= 8, ry >= 0, rx >= 0 and 1 <= h, w <= 32767; n == 0 is a no-op. */
+int spr_surface_peaks(const float* surfaces, int64_t n, int32_t h, int32_t w, int32_t n_peaks, int32_t ry, int32_t rx,
+                      float* out_value, int32_t* out_yx, float* out_psr, spr_stream_t stream);
 
 /* ------------------------------------------------------------------ device-resident ragged sets (features.py)
  * spr_items_gather: item k of dst (k < n) is item index[k] of src, converted to dst_dtype (an spr_dtype).  src: device

@@ -73,11 +73,15 @@ SIGNATURES = {
     "spr_ncc_score_peaks": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _I64, _I64, C.c_int, _I32, _VP]),
     "spr_ncc_plan_has_list": (C.c_int, [_VP]),
     "spr_ncc_score_list": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, C.c_int, _I32, _VP]),
+    "spr_ncc_plan_has_surfaces": (C.c_int, [_VP]),
+    "spr_ncc_score_surfaces": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, C.c_int, _I32, _VP]),
     "spr_rank_true_match": (C.c_int, [_VP, _I64, _I64, _I64, _VP, _VP, _VP]),
     "spr_rank_count_greater": (C.c_int, [_VP, _I64, _I64, _I64, _I64, _VP, _VP, _VP, _VP]),
     "spr_scores_fuse": (C.c_int, [_VP, _VP, _I64, C.c_float, C.c_float, _VP]),
     "spr_topk_rows": (C.c_int, [_VP, _I64, _I64, _I64, _VP, _I64, _I32, _VP, _VP, _VP]),
     "spr_maps_peak": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _VP, _VP, _VP]),
+    "spr_maps_mean": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _VP, _VP]),
+    "spr_surface_peaks": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
     "spr_items_gather": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _I32, _VP]),
     "spr_block_scatter": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _I32, _VP]),
     "spr_rotate_nearest":(C.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, C.POINTER(_I64), _VP]),

@@ -11,6 +11,8 @@
 * ``topk(scores, k) -> (float32 [Q, k], int32 [Q, k])``                                 (the k best items per row, ranker's order)
 * ``ncc_scores_located(q, g, crop=2, method="auto", max_prepared_bytes=0) -> (float32 [Q, G], int32 [Q, G, 2])``
   (``ncc_scores`` and the pixel at which every pair's NCC map peaks, (-1, -1) where the score is 0; "fft" / "direct" plans)
+* ``surface_peaks(surfaces, n_peaks, ry, rx) -> (float32 [n, n_peaks], int32 [n, n_peaks], float32 [n])``
+  (the best separated peaks of every correlation surface, positions packed ``(y << 16) | x``, and the peak-to-sidelobe ratio)
 
 They take GPU tensors, run on PyTorch's current HIP stream and never synchronise; the ctypes route (``_lib.py``) calls the
 very same entry points.  ``SPR_TORCH_OPS=0`` keeps the host mirror on the ctypes route (A/B and parity tests).

@@ -372,6 +372,31 @@ extern "C" int spr_ncc_score_list(spr_ncc_plan* plan, const void* pq, int64_t nq
   return score_pairs(plan, c);
 }
 
+extern "C" int spr_ncc_plan_has_surfaces(const spr_ncc_plan* plan) { return spr_ncc_plan_has_list(plan); }
+
+extern "C" int spr_ncc_score_surfaces(spr_ncc_plan* plan, const void* pq, int64_t nq, const void* pg, int64_t ng,
+                                      const int32_t* pairs, int64_t n_pairs, float* scores, int32_t* peak_yx, int32_t* peak_tag,
+                                      float* surfaces, int accumulate_max, int32_t tag, spr_stream_t stream) {
+  if (!plan) { set_error("spr_ncc_score_surfaces: null plan"); return SPR_ERR_ARG; }
+  if (!spr_ncc_plan_has_surfaces(plan)) {  // before anything is launched
+    set_error("spr_ncc_score_surfaces: the workspace instance of the FFT method and the matrix-core methods have no surfaces "
+              "form (spr_ncc_plan_has_surfaces() == 0)");
+    return SPR_ERR_UNSUPPORTED;
+  }
+  if (nq < 0 || ng < 0 || n_pairs < 0) { set_error("spr_ncc_score_surfaces: bad sizes"); return SPR_ERR_ARG; }
+  if (n_pairs == 0) return SPR_OK;
+  if (!pq || !pg || !pairs || !scores || !peak_yx || !surfaces) { set_error("spr_ncc_score_surfaces: null pointer"); return SPR_ERR_ARG; }
+  if (nq > 65535 || ng > (1 << 24)) { set_error("spr_ncc_score_surfaces: too many items in one call (chunk the gallery)"); return SPR_ERR_ARG; }
+  PairCall c{pq, nq, pg, ng, scores, n_pairs, 0, accumulate_max, nullptr, static_cast<hipStream_t>(stream)};
+  c.peak_yx = peak_yx;
+  c.peak_tag = peak_tag;
+  c.tag = tag;
+  c.pairs = pairs;
+  c.n_pairs = n_pairs;
+  c.surfaces = surfaces;
+  return score_pairs(plan, c);
+}
+
 extern "C" int spr_ncc_maps(spr_ncc_plan* plan, const void* pq, const void* pg, float* maps_out, spr_stream_t stream) {
   if (!plan || !pq || !pg || !maps_out) { set_error("spr_ncc_maps: null pointer"); return SPR_ERR_ARG; }
   return score_pairs(plan, PairCall{pq, 1, pg, 1, nullptr, 1, 0, 0, maps_out, static_cast<hipStream_t>(stream)});

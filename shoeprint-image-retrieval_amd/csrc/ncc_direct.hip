@@ -9,11 +9,19 @@
 // This is the simple path: arithmetic = th*tw*pad... multiply-adds per output pixel including
 // the zero padding.  The FFT method (ncc_pair_fft.hip) is the fast path; this one covers every
 // shape that fits LDS and cross-checks the FFT path on the GPU.
+#include <type_traits>
+
 #include "ncc_prep_common.h"
 
 namespace spr {
 
 namespace {
+
+// The surfaces form's geometry argument: the plan's, and behind it where the maps go.  An argument struct of its own, so that
+// the kernel arguments of every other form lie where they lay.
+struct NccGeomSurf : NccGeom {
+  float* surfaces;  // device float32 [entries of the list][ih][iw]
+};
 
 __host__ __device__ inline int round_up8(int v) { return (v + 7) / 8 * 8; }
 
@@ -63,9 +71,11 @@ prep_direct_kernel(NccGeom g, int is_query, const void* __restrict__ maps, float
 // LIST: the form behind spr_ncc_score_list, a peak form on a 1-D grid: workgroup w takes entry col0 + w of a device list of
 // (query, gallery) positions.  The list rides in `maps_out`, its length in `ld`, and the item counts every entry is tested
 // against in g.nh / g.nw, FFT fields this method has no use for: the form has no parameters of its own.
-template <int SPT, bool PEAKS, bool LIST>
+// SURF: the form behind spr_ncc_score_surfaces, a list form that also stores the entry's channel-mean map, total / channels,
+// where its (score, peak, tag) is written; the form is told by its geometry argument (G = NccGeomSurf).
+template <int SPT, bool PEAKS, bool LIST, class G = NccGeom>
 __global__ void __launch_bounds__(kThreads)
-pair_direct_kernel(NccGeom g, const float* __restrict__ pq, size_t q_item_floats, const float* __restrict__ pg,
+pair_direct_kernel(G g, const float* __restrict__ pq, size_t q_item_floats, const float* __restrict__ pg,
                    size_t g_item_floats, float* __restrict__ scores, long long ld, long long col0, int accumulate,
                    float* __restrict__ maps_out, int pws, int tws, unsigned t_off, int32_t* __restrict__ peak_yx,
                    int32_t* __restrict__ peak_tag, int32_t tag) {
@@ -165,7 +175,27 @@ pair_direct_kernel(NccGeom g, const float* __restrict__ pq, size_t q_item_floats
       }
     }
     block_peak(best, where, red);
-    if (tid == 0)
+    if constexpr (std::is_same<G, NccGeomSurf>::value) {
+      // work-item 0 decides, as it does in the list form, and tells the others through a spare word of the reduction scratch
+      // (block_peak uses 8 of its 16); then every work-item stores the pixels it owns
+      static_assert(LIST, "the surfaces form is a list form");
+      int* told = reinterpret_cast<int*>(red) + 15;
+      if (tid == 0)
+        *told = store_peak(scores, peak_yx, peak_tag, list_at, best / static_cast<float>(g.channels), where, tag, accumulate) ? 1 : 0;
+      __syncthreads();
+      if (*told) {
+        float* dst = g.surfaces + list_at * static_cast<size_t>(n_img);
+        const float channels = static_cast<float>(g.channels);
+#pragma unroll
+        for (int k = 0; k < SPT; ++k) {
+#pragma unroll
+          for (int j = 0; j < kStrip; ++j) {
+            if (sy[k] < g.ih && sx[k] + j < g.iw) dst[sy[k] * g.iw + sx[k] + j] = total[k][j] / channels;
+          }
+        }
+      }
+      return;
+    } else if (tid == 0)
       store_peak(scores, peak_yx, peak_tag, LIST ? list_at : qi * ld + col0 + gi, best / static_cast<float>(g.channels), where, tag, accumulate);
     return;
   }
@@ -230,21 +260,23 @@ int launch_prep_direct(const NccGeom& g, const PlanScratch&, const PrepCall& c) 
   return check_launch("prep_direct_kernel");
 }
 
-template <int SPT, bool PEAKS, bool LIST = false>
+template <int SPT, bool PEAKS, bool LIST = false, class G = NccGeom>
 static int launch_pair_direct_t(const NccGeom& g, const PlanScratch&, const PairCall& c) {
   const DirectLds l = direct_lds(g);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pair_direct_kernel<SPT, PEAKS, LIST>),
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pair_direct_kernel<SPT, PEAKS, LIST, G>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
   // grid = (gallery, query) workgroups; HIP refuses 2^32 work-items and more along x: slices of the gallery
   const size_t g_item_floats = prepared_gallery_item_bytes(g, SPR_NCC_DIRECT) / sizeof(float);
   const int64_t max_g = pair_tiles_per_launch(1, kThreads);
   if constexpr (LIST) {  // one workgroup per entry, sliced like the gallery below
-    NccGeom gl = g;
+    G gl{};
+    static_cast<NccGeom&>(gl) = g;
     gl.nh = static_cast<int>(c.nq);  // (see the kernel)
     gl.nw = static_cast<int>(c.ng);
+    if constexpr (std::is_same<G, NccGeomSurf>::value) gl.surfaces = c.surfaces;
     for (int64_t e0 = 0; e0 < c.n_pairs; e0 += max_g) {
       const int64_t n = c.n_pairs - e0 < max_g ? c.n_pairs - e0 : max_g;
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_direct_kernel<SPT, PEAKS, LIST>), dim3(static_cast<unsigned>(n)), dim3(kThreads),
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_direct_kernel<SPT, PEAKS, LIST, G>), dim3(static_cast<unsigned>(n)), dim3(kThreads),
                          l.total, c.stream, gl, static_cast<const float*>(c.pq),
                          prepared_query_item_bytes(g, SPR_NCC_DIRECT) / sizeof(float), static_cast<const float*>(c.pg),
                          g_item_floats, c.scores, static_cast<long long>(c.n_pairs), static_cast<long long>(e0), c.accumulate,
@@ -255,10 +287,12 @@ static int launch_pair_direct_t(const NccGeom& g, const PlanScratch&, const Pair
     }
     return SPR_OK;
   }
+  G gd{};  // (the dense forms: G = NccGeom)
+  static_cast<NccGeom&>(gd) = g;
   for (int64_t g0 = 0; g0 < c.ng; g0 += max_g) {
     const int64_t n = c.ng - g0 < max_g ? c.ng - g0 : max_g;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_direct_kernel<SPT, PEAKS, LIST>), dim3(static_cast<unsigned>(n), static_cast<unsigned>(c.nq)),
-                       dim3(kThreads), l.total, c.stream, g, static_cast<const float*>(c.pq),
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_direct_kernel<SPT, PEAKS, LIST, G>), dim3(static_cast<unsigned>(n), static_cast<unsigned>(c.nq)),
+                       dim3(kThreads), l.total, c.stream, gd, static_cast<const float*>(c.pq),
                        prepared_query_item_bytes(g, SPR_NCC_DIRECT) / sizeof(float),
                        static_cast<const float*>(c.pg) + static_cast<size_t>(g0) * g_item_floats, g_item_floats, c.scores,
                        static_cast<long long>(c.ld), static_cast<long long>(c.col0 + g0), c.accumulate, c.maps_out, l.pws,
@@ -270,6 +304,16 @@ static int launch_pair_direct_t(const NccGeom& g, const PlanScratch&, const Pair
 }
 
 int launch_pair_direct(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
+  if (c.pairs && c.surfaces) {  // spr_ncc_score_surfaces
+    if (c.n_pairs == 0) return SPR_OK;
+    switch (g.strips_per_thread) {
+      case 1: return launch_pair_direct_t<1, true, true, NccGeomSurf>(g, s, c);
+      case 2: return launch_pair_direct_t<2, true, true, NccGeomSurf>(g, s, c);
+      case 4: return launch_pair_direct_t<4, true, true, NccGeomSurf>(g, s, c);
+      case 8: return launch_pair_direct_t<8, true, true, NccGeomSurf>(g, s, c);
+      default: set_error("direct NCC: unsupported strips per thread %d", g.strips_per_thread); return SPR_ERR_UNSUPPORTED;
+    }
+  }
   if (c.pairs) {  // spr_ncc_score_list
     if (c.n_pairs == 0) return SPR_OK;
     switch (g.strips_per_thread) {

@@ -55,6 +55,7 @@ int launch_prep_fft(const NccGeom& g, const PlanScratch& s, const PrepCall& c) {
 }
 
 int launch_pair_fft(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
+  if (c.pairs && c.surfaces) return c.n_pairs == 0 ? SPR_OK : launch_pair_fft_surfaces(g, s, c);  // (ncc_fft_surfaces.hip)
   if (c.pairs) return c.n_pairs == 0 ? SPR_OK : launch_pair_fft_list(g, s, c);  // the LIST instances (ncc_fft_list.hip)
   if (c.nq == 0 || c.ng == 0) return SPR_OK;
   const FftEntry* e = find_entry(g.nh, g.nw, g.six);

@@ -1,7 +1,8 @@
 // FFT-method NCC scorer (the fast path): kernels, launchers and the table of instances.  Included by the three translation
 // units that instantiate them - ncc_fft.hip (prep kernels, plain pair kernels, the public functions of the method),
-// ncc_fft_peaks.hip (the pair kernels in their peak form, SPR_FFT_PEAKS_TU defined before the include) and ncc_fft_list.hip
-// (the peak form over a list of pairs, SPR_FFT_LIST_TU).
+// ncc_fft_peaks.hip (the pair kernels in their peak form, SPR_FFT_PEAKS_TU defined before the include), ncc_fft_list.hip
+// (the peak form over a list of pairs, SPR_FFT_LIST_TU) and ncc_fft_surfaces.hip (the list form that stores the map too,
+// SPR_FFT_SURF_TU).
 //
 // Correlation theorem:  num = IFFT2( FFT2(I0z) . conj(FFT2(t^)) )  on an nh x nw grid large enough
 // that the 'same'-mode lags are free of circular aliasing (nh >= ih + max(th/2, th-1-th/2), same
@@ -323,17 +324,25 @@ struct PairArgs {
 // entry col0 + blockIdx.x of a device list of (query, gallery) positions instead of a cell of the tile mapping.  It has no
 // parameters of its own (see PairArgs::kernarg_pad): the list rides in `maps_out`, its length in `ld`, the launch's first
 // entry in `col0` - three parameters a list launch has no other use for.  LDS-mode instances only.
-#ifdef SPR_FFT_LIST_TU
+// SURF: the form behind spr_ncc_score_surfaces (ncc_fft_surfaces.hip defines SPR_FFT_SURF_TU) - a list form that also stores
+// the entry's channel-mean map, acc / channels, where its (score, peak, tag) is written.  The map's buffer rides in `ws`, which
+// an LDS-mode launch has no other use for.  Only the epilogue differs.
+#ifdef SPR_FFT_SURF_TU
+constexpr bool kSurfTu = true;
+#else
+constexpr bool kSurfTu = false;
+#endif
+#if defined(SPR_FFT_LIST_TU) || defined(SPR_FFT_SURF_TU)
 constexpr bool kListTu = true;
 #else
 constexpr bool kListTu = false;
 #endif
-#if defined(SPR_FFT_PEAKS_TU) || defined(SPR_FFT_LIST_TU)
+#if defined(SPR_FFT_PEAKS_TU) || defined(SPR_FFT_LIST_TU) || defined(SPR_FFT_SURF_TU)
 constexpr bool kPeaksTu = true;
 #else
 constexpr bool kPeaksTu = false;
 #endif
-template <class C, int RR, int KW, int PF, int RK, bool BIG, bool PEAKS, bool LIST>
+template <class C, int RR, int KW, int PF, int RK, bool BIG, bool PEAKS, bool LIST, bool SURF>
 __global__ void __launch_bounds__(C::NT, BIG ? 1 : ((C::NT == 64 && RK > 0) ? 4 : 2))
 pair_fft_kernel(PairArgs g, const unsigned char* __restrict__ pq, size_t q_item_bytes,
                 const unsigned char* __restrict__ pg, size_t g_item_bytes, float* __restrict__ scores,
@@ -696,8 +705,45 @@ pair_fft_kernel(PairArgs g, const unsigned char* __restrict__ pq, size_t q_item_
         }
       }
     }
+    if constexpr (SURF) {
+      // spr_ncc_score_surfaces: the channel sums leave the registers for the image's place in LDS (dead since the channel
+      // loop's last barrier; NW/2 columns of >= r_rows complex values hold ih x iw floats), every slot at the pixel the maps
+      // branch would store it to - the accumulators are dead before the reduction starts, so the form spills no more than
+      // its list sibling, and the map goes out below in rows of consecutive words
+      static_assert(LIST && !BIG, "the surfaces form is a list form: LDS-mode instances only");
+      float* tile = reinterpret_cast<float*>(lds + r_off);
+#pragma unroll
+      for (int r = 0; r < RR; ++r) {
+        const int n1 = 2 * (r * C::PPR + gr);
+#pragma unroll
+        for (int pp = 0; pp < GW::SPL; ++pp) {
+#pragma unroll
+          for (int s = 0; s < KW; ++s) {
+            const int e = (pp * KW + s) * 2;
+            const int n2 = GW::out_index(tr, pp, s);
+            const bool ok = r < g.rounds_r && GW::out_valid(tr, pp) && n2 < g.iw;
+            if (ok && n1 < g.ih) tile[n1 * g.iw + n2] = acc[r][e];
+            if (ok && n1 + 1 < g.ih) tile[(n1 + 1) * g.iw + n2] = acc[r][e + 1];
+          }
+        }
+      }
+    }
     block_peak<C::NT>(best, where, red);
-    if (tid == 0)
+    if constexpr (SURF) {
+      // work-item 0 decides, as it does in the list form, and tells the others through a word of the exchange buffers (dead
+      // as the image is); the barrier also puts the tile's stores before its reads
+      int* told = reinterpret_cast<int*>(lds + xbuf_off);
+      if (tid == 0)
+        *told = store_peak(scores, peak_yx, peak_tag, list_at, best / static_cast<float>(g.channels), where, tag, g.accumulate) ? 1 : 0;
+      __syncthreads();
+      if (*told) {
+        const int pixels = g.ih * g.iw;
+        float* dst = reinterpret_cast<float*>(ws) + list_at * static_cast<size_t>(pixels);
+        const float channels = static_cast<float>(g.channels);
+        const float* tile = reinterpret_cast<const float*>(lds + r_off);
+        for (int i = tid; i < pixels; i += C::NT) dst[i] = tile[i] / channels;
+      }
+    } else if (tid == 0)
       store_peak(scores, peak_yx, peak_tag, LIST ? list_at : static_cast<size_t>(qi) * ld + col0 + gi_item,
                  best / static_cast<float>(g.channels), where, tag, g.accumulate);
   } else {
@@ -866,23 +912,24 @@ int pair_launch(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
   a.channels = g.channels; a.nq = static_cast<int>(nq); a.ng = static_cast<int>(ng);
   a.ih = g.ih; a.iw = g.iw; a.r_rows = g.r_rows; a.r_stride = g.r_stride; a.rounds_r = g.rounds_r;
   a.inv_per_chan = g.inv_per_chan; a.accumulate = c.accumulate;
-  const void* kernel = reinterpret_cast<const void*>(pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu, kListTu>);
+  const void* kernel = reinterpret_cast<const void*>(pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu, kListTu, kSurfTu>);
   (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
   if constexpr (kListTu) {
     // list mode: one workgroup per entry, in slices of as many entries as a dense launch holds pairs; the list goes down in
-    // `maps_out`, its length in `ld`, the slice's first entry in `col0` (see the kernel)
+    // `maps_out`, its length in `ld`, the slice's first entry in `col0`, the surfaces form's maps in `ws` (see the kernel)
     static_assert(!BIG, "the list form has LDS-mode instances only");
     const int64_t max_entries = pair_tiles_per_launch(kTileQ * kTileG, C::NT) * (kTileQ * kTileG);
     for (int64_t e0 = 0; e0 < c.n_pairs; e0 += max_entries) {
       const int64_t n = c.n_pairs - e0 < max_entries ? c.n_pairs - e0 : max_entries;
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu, kListTu>),
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu, kListTu, kSurfTu>),
                          dim3(static_cast<unsigned>(n)), dim3(C::NT), l.total, c.stream, a,
                          static_cast<const unsigned char*>(c.pq), prepared_query_item_bytes(g, SPR_NCC_FFT),
                          static_cast<const unsigned char*>(c.pg), prepared_gallery_item_bytes(g, SPR_NCC_FFT), c.scores,
                          static_cast<long long>(c.n_pairs), static_cast<long long>(e0),
                          reinterpret_cast<float*>(const_cast<int32_t*>(c.pairs)), s.tw_h, s.tw_w,
                          static_cast<unsigned>(l.r_off), static_cast<unsigned>(l.xbuf_off), static_cast<unsigned>(l.nyq_off),
-                         static_cast<unsigned char*>(nullptr), l.slot_bytes, c.peak_yx, c.peak_tag, c.tag);
+                         reinterpret_cast<unsigned char*>(kSurfTu ? c.surfaces : nullptr), l.slot_bytes, c.peak_yx, c.peak_tag,
+                         c.tag);
       const int rc = check_launch("pair_fft_kernel (list)");
       if (rc != SPR_OK) return rc;
     }
@@ -894,7 +941,7 @@ int pair_launch(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
   int per_cu = 0, cus = 0, dev = 0;
   if (BIG && hipGetDevice(&dev) == hipSuccess &&
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu, kListTu>, C::NT, l.total) == hipSuccess &&
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu, kListTu, kSurfTu>, C::NT, l.total) == hipSuccess &&
       per_cu > 0 && cus >= 8) {
     int team_size = cus / 8 * per_cu;
     const size_t slots = s.ws ? s.ws_bytes / l.slot_bytes : 0;
@@ -920,7 +967,7 @@ int pair_launch(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
       a.tile0 = static_cast<int>(t0);
       grid = static_cast<unsigned>(n * kTileQ * kTileG);
     }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu, kListTu>), dim3(grid),
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_fft_kernel<C, RR, KW, PF, RK, BIG, kPeaksTu, kListTu, kSurfTu>), dim3(grid),
                        dim3(C::NT), l.total, c.stream, a, static_cast<const unsigned char*>(c.pq),
                        prepared_query_item_bytes(g, SPR_NCC_FFT), static_cast<const unsigned char*>(c.pg),
                        prepared_gallery_item_bytes(g, SPR_NCC_FFT), c.scores,

@@ -22,6 +22,7 @@
 // LDS per workgroup (145 KB): per pair {image 48 x 139 complex | per-wave exchange rows | Nyquist products},
 // shared {column twiddles | pre-twist table}.
 #include <cstdlib>
+#include <type_traits>
 
 #include "fft_core.h"
 #include "ncc_fft_cfg.h"
@@ -62,6 +63,11 @@ struct Pair6Args {
   int tiles_g;  // pair tiles along the gallery
   int prio_mode;  // experiment: static wave priorities (SPR_P6_PRIO)
   unsigned q_flags_off, g_flags_off;  // byte offset of the per-channel dead flags inside a prepared item
+};
+// The surfaces form's arguments: the same, and behind them where the maps go.  An argument struct of its own, so that the
+// kernel arguments of every other form lie where they lay.
+struct Pair6SurfArgs : Pair6Args {
+  float* surfaces;  // device float32 [entries of the list][ih][iw]
 };
 
 // 12-point transform as 3 x 4 (Good-Thomas): input n = (4 n1 + 3 n2) mod 12, output k = (4 k1 + 9 k2) mod 12,
@@ -134,9 +140,11 @@ struct Six {
 // carries nothing of it.  Only the epilogue differs.  MAPS: the form behind spr_ncc_maps, likewise - its stores sit inside the
 // accumulation of the row pass, where even a not-taken branch per accumulator set cuts the scoring forms into basic blocks.
 // LIST: the form behind spr_ncc_score_list, a peak form whose two halves take two entries of a list of pairs ("which pairs").
-template <class C, bool PEAKS, bool MAPS, bool LIST>
+// SURF: the form behind spr_ncc_score_surfaces, a list form that also stores a half's channel-mean map, acc / channels, where
+// its (score, peak, tag) is written.  Only the epilogue differs; the form is told by its argument struct (A = Pair6SurfArgs).
+template <class C, bool PEAKS, bool MAPS, bool LIST, class A = Pair6Args>
 __global__ void __launch_bounds__(2 * C::NT, 3)
-pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_bytes,
+pair6_kernel(A g, const unsigned char* __restrict__ pq, size_t q_item_bytes,
              const unsigned char* __restrict__ pg, size_t g_item_bytes, float* __restrict__ scores, long long ld,
              long long col0, float* __restrict__ maps_out, const cf* __restrict__ tw_h,
              const float* __restrict__ ctab, int32_t* __restrict__ peak_yx, int32_t* __restrict__ peak_tag,
@@ -144,6 +152,8 @@ pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_by
   using S = Six<C>;
   constexpr int NT = S::NT, RS = S::RS, XR = S::XR;
   constexpr int H2 = C::EH / 2;  // 16-byte loads per operand and column unit
+  constexpr bool SURF = std::is_same<A, Pair6SurfArgs>::value;
+  static_assert(!SURF || (LIST && PEAKS), "the surfaces form is a list form");
 
   // ---- which pairs ------------------------------------------------------------------------------
   // A workgroup scores two queries against one gallery item: lanes [0, 384) the first pair, [384, 768) the second, each
@@ -571,12 +581,36 @@ pair6_kernel(Pair6Args g, const unsigned char* __restrict__ pq, size_t q_item_by
       red_pos[wv] = where;
     }
     __syncthreads();
+    bool stored = false;
     if (tid0 == 0 && live) {
       float b = red[0];
       int p = red_pos[0];
       for (int w = 1; w < S::WAVES; ++w) peak_take(b, p, red[w], red_pos[w]);
-      store_peak(scores, peak_yx, peak_tag, LIST ? list_at : static_cast<size_t>(qi) * ld + col0 + gi_item,
-                 b / static_cast<float>(g.channels), p, tag, g.accumulate);
+      stored = store_peak(scores, peak_yx, peak_tag, LIST ? list_at : static_cast<size_t>(qi) * ld + col0 + gi_item,
+                          b / static_cast<float>(g.channels), p, tag, g.accumulate);
+    }
+    if constexpr (SURF) {
+      // Each half decides for itself and tells its lanes through the spare word of its reduction scratch (the six waves
+      // use words 0..5 of eight); the barrier in between is the workgroup's, so both halves pass it whatever either decided.
+      // An idle half - the odd entry of a list, an entry that names no item - stores nothing: its lane 0 says so.
+      int* told = reinterpret_cast<int*>(red) + 7;
+      if (tid0 == 0) *told = stored ? 1 : 0;
+      __syncthreads();
+      if (*told && row_ok) {
+        float* dst = g.surfaces + (list_at * g.ih + real_row) * static_cast<size_t>(g.iw);
+        const float channels = static_cast<float>(g.channels);
+#pragma unroll
+        for (int pp = 0; pp < 6; ++pp) {
+          const int n1 = t3 + 3 * pp;
+          const int ma = t3 == 2 ? n1 + 16 : n1, mb = t3 == 2 ? n1 : n1 + 16;
+          if (n1 < 16) {
+            if (2 * ma < g.iw) dst[2 * ma] = acc[pp][0].x / channels;
+            if (2 * ma + 1 < g.iw) dst[2 * ma + 1] = acc[pp][0].y / channels;
+            if (2 * mb < g.iw) dst[2 * mb] = acc[pp][1].x / channels;
+            if (2 * mb + 1 < g.iw) dst[2 * mb + 1] = acc[pp][1].y / channels;
+          }
+        }
+      }
     }
     return;
   }
@@ -615,11 +649,12 @@ size_t pair6_lds_bytes() { return Six<C6>::kLdsBytes; }
 int pair6_max_rows() { return C6::kRows6; }
 int pair6_max_cols() { return 64; }  // outputs x[2m], x[2m+1] for m < 32
 
-template <bool PEAKS, bool MAPS, bool LIST = false>
+template <bool PEAKS, bool MAPS, bool LIST = false, class A = Pair6Args>
 static int launch_pair6_t(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
   if (!s.six_ctab) { set_error("pair6_kernel: the plan has no pre-twist table"); return SPR_ERR_ARG; }
   using S = Six<C6>;
-  Pair6Args a{};
+  A a{};
+  if constexpr (std::is_same<A, Pair6SurfArgs>::value) a.surfaces = c.surfaces;
   a.channels = g.channels; a.nq = static_cast<int>(c.nq); a.ng = static_cast<int>(c.ng);
   a.ih = g.ih; a.iw = g.iw; a.inv_per_chan = g.inv_per_chan; a.accumulate = c.accumulate;
   a.tiles_g = ceil_div(static_cast<int>(c.ng), kTileG6);
@@ -630,7 +665,7 @@ static int launch_pair6_t(const NccGeom& g, const PlanScratch& s, const PairCall
   const size_t lds_bytes = S::kLdsBytes + 2 * sizeof(unsigned short) * static_cast<size_t>(g.channels);
   a.prio_mode = env_int("SPR_P6_PRIO", 2);
   const int64_t tiles = static_cast<int64_t>(ceil_div(static_cast<int>(c.nq), kTileQ6)) * a.tiles_g;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pair6_kernel<C6, PEAKS, MAPS, LIST>), hipFuncAttributeMaxDynamicSharedMemorySize,
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pair6_kernel<C6, PEAKS, MAPS, LIST, A>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             kLdsLimit);
   // HIP refuses grids of 2^32 work-items and more: launch in slices of pair tiles
   const int64_t max_tiles = pair_tiles_per_launch(kTileQ6 * kTileG6 / 2, 2 * C6::NT);
@@ -641,7 +676,7 @@ static int launch_pair6_t(const NccGeom& g, const PlanScratch& s, const PairCall
     const int64_t max_entries = max_tiles * (kTileQ6 * kTileG6);
     for (int64_t e0 = 0; e0 < c.n_pairs; e0 += max_entries) {
       const int64_t n = c.n_pairs - e0 < max_entries ? c.n_pairs - e0 : max_entries;
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(pair6_kernel<C6, PEAKS, MAPS, LIST>), dim3(static_cast<unsigned>((n + 1) / 2)), dim3(2 * C6::NT),
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(pair6_kernel<C6, PEAKS, MAPS, LIST, A>), dim3(static_cast<unsigned>((n + 1) / 2)), dim3(2 * C6::NT),
                          lds_bytes, c.stream, a, static_cast<const unsigned char*>(c.pq),
                          prepared_query_item_bytes(g, SPR_NCC_FFT), static_cast<const unsigned char*>(c.pg),
                          prepared_gallery_item_bytes(g, SPR_NCC_FFT), c.scores, static_cast<long long>(c.n_pairs),
@@ -655,7 +690,7 @@ static int launch_pair6_t(const NccGeom& g, const PlanScratch& s, const PairCall
   for (int64_t t0 = 0; t0 < tiles; t0 += max_tiles) {
     const int64_t n = tiles - t0 < max_tiles ? tiles - t0 : max_tiles;
     a.tile0 = static_cast<int>(t0);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair6_kernel<C6, PEAKS, MAPS, LIST>), dim3(static_cast<unsigned>(n * (kTileQ6 * kTileG6 / 2))), dim3(2 * C6::NT),
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair6_kernel<C6, PEAKS, MAPS, LIST, A>), dim3(static_cast<unsigned>(n * (kTileQ6 * kTileG6 / 2))), dim3(2 * C6::NT),
                        lds_bytes, c.stream, a, static_cast<const unsigned char*>(c.pq),
                        prepared_query_item_bytes(g, SPR_NCC_FFT), static_cast<const unsigned char*>(c.pg),
                        prepared_gallery_item_bytes(g, SPR_NCC_FFT), c.scores, static_cast<long long>(c.ld),
@@ -667,6 +702,7 @@ static int launch_pair6_t(const NccGeom& g, const PlanScratch& s, const PairCall
 }
 
 int launch_pair6(const NccGeom& g, const PlanScratch& s, const PairCall& c) {
+  if (c.pairs && c.surfaces) return c.n_pairs == 0 ? SPR_OK : launch_pair6_t<true, false, true, Pair6SurfArgs>(g, s, c);  // spr_ncc_score_surfaces
   if (c.pairs) return c.n_pairs == 0 ? SPR_OK : launch_pair6_t<true, false, true>(g, s, c);  // spr_ncc_score_list
   if (c.nq == 0 || c.ng == 0) return SPR_OK;
   if (c.peak_yx) return launch_pair6_t<true, false>(g, s, c);

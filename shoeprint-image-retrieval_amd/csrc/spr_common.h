@@ -82,6 +82,9 @@ struct PairCall {
   // entry per pair (ld and col0 mean nothing), nq and ng are what the kernels test every entry against.  Always with peak_yx.
   const int32_t* pairs = nullptr;
   int64_t n_pairs = 0;
+  // spr_ncc_score_surfaces: the list form that also stores every entry's channel-mean map, device float32 [n_pairs][ih][iw];
+  // null = spr_ncc_score_list.  Always with pairs.
+  float* surfaces = nullptr;
 };
 struct PrepCall {
   bool is_query;
@@ -107,6 +110,7 @@ int launch_prep_fft(const NccGeom& g, const PlanScratch& s, const PrepCall& c);
 int launch_pair_fft(const NccGeom& g, const PlanScratch& s, const PairCall& c);
 int launch_pair_fft_peaks(const NccGeom& g, const PlanScratch& s, const PairCall& c);  // c.peak_yx set (ncc_fft_peaks.hip)
 int launch_pair_fft_list(const NccGeom& g, const PlanScratch& s, const PairCall& c);   // c.pairs set (ncc_fft_list.hip)
+int launch_pair_fft_surfaces(const NccGeom& g, const PlanScratch& s, const PairCall& c);  // c.surfaces set (ncc_fft_surfaces.hip)
 int launch_pair6(const NccGeom& g, const PlanScratch& s, const PairCall& c);  // six-wave pair kernel (ncc_pair6.hip)
 bool prep6_covers(const NccGeom& g);  // gallery of a six-wave plan with corner windows (ncc_prep6.hip)
 int launch_prep6(const NccGeom& g, const PlanScratch& s, const PrepCall& c);
@@ -239,15 +243,16 @@ __device__ __forceinline__ void block_peak(float& v, int& p, float* scratch) {
   for (int w = 1; w < NT / 64; ++w) peak_take(v, p, scratch[w], pos[w]);
 }
 // One entry of spr_ncc_score_peaks (the contract is in the header).  s = the pair's score, p = the position of the map's
-// maximum; `scores` receives what the plain form stores.
-__device__ __forceinline__ void store_peak(float* scores, int32_t* peak_yx, int32_t* peak_tag, size_t at, float s, int p,
+// maximum; `scores` receives what the plain form stores.  Returns whether the entry was written: the surfaces form
+// (spr_ncc_score_surfaces) stores the pair's map exactly then.
+__device__ __forceinline__ bool store_peak(float* scores, int32_t* peak_yx, int32_t* peak_tag, size_t at, float s, int p,
                                            int32_t tag, int accumulate) {
   const bool hit = s > 0.0f;  // (only then is p a pixel that won)
   if (!accumulate) {
     scores[at] = hit ? s : 0.0f;
     peak_yx[at] = hit ? p : -1;
     if (peak_tag) peak_tag[at] = hit ? tag : -1;
-    return;
+    return true;
   }
   const float prev = scores[at];
   bool take = s > prev;
@@ -257,6 +262,7 @@ __device__ __forceinline__ void store_peak(float* scores, int32_t* peak_yx, int3
     peak_yx[at] = hit ? p : -1;
     if (peak_tag) peak_tag[at] = hit ? tag : -1;
   }
+  return take;
 }
 
 }  // namespace spr

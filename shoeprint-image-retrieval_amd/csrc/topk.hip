@@ -9,6 +9,11 @@
 // spr_maps_peak sums the per-channel maps of spr_ncc_maps in float64, channel 0 first - a fixed order: the result is
 // bit-reproducible - and reduces the summed map to its first maximum in row-major order.  A work-item owns its pixels and
 // walks the channels, so the loads of a wave are coalesced across pixels.  HBM-bound: 4 bytes per map value.
+// spr_maps_mean is the same sum with every pixel kept: the channel-mean map of a pair whose plan has no surfaces form.
+//
+// spr_surface_peaks reads a channel-mean map (spr_ncc_score_surfaces, spr_maps_mean) the way an examiner does: its n best
+// peaks, each outside the windows of the ones before it, and the peak-to-sidelobe ratio of the first.  One workgroup per
+// surface, one pass over it per peak and two for the ratio; a surface is tens of KB and stays in L2.
 #include "spr_common.h"
 
 namespace spr {
@@ -152,6 +157,98 @@ maps_peak_kernel(const float* __restrict__ maps, long long n_pairs, int channels
   }
 }
 
+// the float64 channel sum of maps_peak_kernel, every pixel kept: out = (float)(acc / channels)
+__global__ void __launch_bounds__(kThreads)
+maps_mean_kernel(const float* __restrict__ maps, long long n_pairs, int channels, int pixels, float* __restrict__ out) {
+  const int tid = static_cast<int>(threadIdx.x);
+  for (long long p = blockIdx.x; p < n_pairs; p += gridDim.x) {
+    const float* pair = maps + static_cast<size_t>(p) * channels * pixels;
+    float* dst = out + static_cast<size_t>(p) * pixels;
+    for (int i = tid; i < pixels; i += kThreads) {
+      const float* px = pair + i;
+      double acc = 0.0;
+      int c = 0;
+      for (; c + 8 <= channels; c += 8) {  // eight loads in flight, added in channel order
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = px[static_cast<size_t>(c + u) * pixels];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc += static_cast<double>(v[u]);
+      }
+      for (; c < channels; ++c) acc += static_cast<double>(px[static_cast<size_t>(c) * pixels]);
+      dst[i] = static_cast<float>(acc / channels);
+    }
+  }
+}
+
+constexpr int kMaxSurfacePeaks = 8;
+
+__global__ void __launch_bounds__(kThreads)
+surface_peaks_kernel(const float* __restrict__ surfaces, long long n, int h, int w, int n_peaks, int ry, int rx,
+                     float* __restrict__ out_value, int* __restrict__ out_yx, float* __restrict__ out_psr) {
+  __shared__ float red[2 * (kThreads / 64)];
+  __shared__ double dred[kThreads / 64];
+  const int tid = static_cast<int>(threadIdx.x);
+  const int pixels = h * w;
+  for (long long p = blockIdx.x; p < n; p += gridDim.x) {  // (workgroup-uniform: the barriers inside are too)
+    const float* s = surfaces + static_cast<size_t>(p) * pixels;
+    int py[kMaxSurfacePeaks], px[kMaxSurfacePeaks];  // the peaks so far: the same in every work-item (registers: the loop
+    float v0 = 0.0f;                                 // over the peaks is unrolled)
+    int found = 0;
+#pragma unroll
+    for (int j = 0; j < kMaxSurfacePeaks; ++j) {
+      if (j >= n_peaks) break;
+      float best = -INFINITY;  // with kNoPeak: loses against every pixel (values are finite)
+      int where = kNoPeak;
+      for (int i = tid; i < pixels; i += kThreads) {
+        const int y = i / w, x = i - y * w;
+        bool open = true;
+#pragma unroll
+        for (int k = 0; k < j; ++k) open = open && (abs(y - py[k]) > ry || abs(x - px[k]) > rx);
+        if (open) peak_take(best, where, s[i], (y << 16) | x);
+      }
+      block_peak(best, where, red);
+      if (where == kNoPeak) break;  // no pixel is left (the same in every work-item)
+      if (tid == 0) {
+        out_value[p * n_peaks + j] = best;
+        out_yx[p * n_peaks + j] = where;
+      }
+      py[j] = where >> 16;
+      px[j] = where & 0xffff;
+      if (j == 0) v0 = best;
+      found = j + 1;
+    }
+    for (int e = found + tid; e < n_peaks; e += kThreads) {  // empty slots
+      out_value[p * n_peaks + e] = 0.0f;
+      out_yx[p * n_peaks + e] = -1;
+    }
+    if (!out_psr) continue;
+    // peak-to-sidelobe ratio of peak 0 over the pixels outside its window, float64, two passes: the mean, then the squares
+    const int y_lo = py[0] - ry > 0 ? py[0] - ry : 0, y_hi = py[0] + ry < h - 1 ? py[0] + ry : h - 1;  // (ry, rx <= 32767:
+    const int x_lo = px[0] - rx > 0 ? px[0] - rx : 0, x_hi = px[0] + rx < w - 1 ? px[0] + rx : w - 1;  //  the launcher clamps)
+    auto outside = [&](int i) {
+      const int y = i / w, x = i - y * w;
+      return y < y_lo || y > y_hi || x < x_lo || x > x_hi;
+    };
+    const int count = pixels - (y_hi - y_lo + 1) * (x_hi - x_lo + 1);
+    double sum = 0.0;
+    for (int i = tid; i < pixels; i += kThreads)
+      if (outside(i)) sum += static_cast<double>(s[i]);
+    sum = block_sum(sum, dred);
+    const double mu = count > 0 ? sum / count : 0.0;
+    double sq = 0.0;
+    for (int i = tid; i < pixels; i += kThreads) {
+      const double d = static_cast<double>(s[i]) - mu;
+      if (outside(i)) sq += d * d;
+    }
+    sq = block_sum(sq, dred);
+    if (tid == 0) {
+      const double sigma = count > 0 ? sqrt(sq / count) : 0.0;
+      out_psr[p] = count < 2 || sigma == 0.0 ? 0.0f : static_cast<float>((static_cast<double>(v0) - mu) / sigma);
+    }
+  }
+}
+
 }  // namespace
 }  // namespace spr
 
@@ -185,4 +282,35 @@ extern "C" int spr_maps_peak(const float* maps, int64_t n_pairs, int32_t channel
                      static_cast<hipStream_t>(stream), maps, static_cast<long long>(n_pairs), static_cast<int>(channels),
                      static_cast<int>(h * w), static_cast<int>(w), out_score, out_yx);
   return check_launch("maps_peak_kernel");
+}
+
+extern "C" int spr_maps_mean(const float* maps, int64_t n_pairs, int32_t channels, int32_t h, int32_t w, float* out,
+                             spr_stream_t stream) {
+  using namespace spr;
+  if (n_pairs < 0 || channels < 1 || h < 1 || w < 1) { set_error("spr_maps_mean: bad sizes"); return SPR_ERR_ARG; }
+  if (static_cast<int64_t>(h) * w > 0x7fffffffLL - kThreads) { set_error("spr_maps_mean: map beyond int32 pixels"); return SPR_ERR_ARG; }
+  if (n_pairs == 0) return SPR_OK;
+  if (!maps || !out) { set_error("spr_maps_mean: null pointer"); return SPR_ERR_ARG; }
+  hipLaunchKernelGGL(maps_mean_kernel, dim3(static_cast<unsigned>(topk_grid(n_pairs))), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), maps, static_cast<long long>(n_pairs), static_cast<int>(channels),
+                     static_cast<int>(h * w), out);
+  return check_launch("maps_mean_kernel");
+}
+
+extern "C" int spr_surface_peaks(const float* surfaces, int64_t n, int32_t h, int32_t w, int32_t n_peaks, int32_t ry, int32_t rx,
+                                 float* out_value, int32_t* out_yx, float* out_psr, spr_stream_t stream) {
+  using namespace spr;
+  if (n < 0 || h < 1 || w < 1 || h > 32767 || w > 32767) { set_error("spr_surface_peaks: bad sizes"); return SPR_ERR_ARG; }
+  if (n_peaks < 1 || n_peaks > kMaxSurfacePeaks || ry < 0 || rx < 0) {
+    set_error("spr_surface_peaks: n_peaks = %d outside [1, %d] or a negative window", n_peaks, kMaxSurfacePeaks);
+    return SPR_ERR_ARG;
+  }
+  if (n == 0) return SPR_OK;
+  if (!surfaces || !out_value || !out_yx) { set_error("spr_surface_peaks: null pointer"); return SPR_ERR_ARG; }
+  hipLaunchKernelGGL(surface_peaks_kernel, dim3(static_cast<unsigned>(topk_grid(n))), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), surfaces, static_cast<long long>(n), static_cast<int>(h),
+                     static_cast<int>(w), static_cast<int>(n_peaks), static_cast<int>(ry < 32767 ? ry : 32767),  // (a window
+                     static_cast<int>(rx < 32767 ? rx : 32767), out_value, out_yx,  // beyond the largest surface covers all of it)
+                     out_psr);
+  return check_launch("surface_peaks_kernel");
 }

@@ -7,6 +7,7 @@
 // and the shortlist behind retrieve() (build-defined: the reference returns ranks of known matches only):
 //   topk(scores [Q,G], k)                  -> (f32 [Q,k], i32 [Q,k])   the k best items of every row, in the ranker's order
 //   ncc_scores_located(q, g)               -> (f32 [Q,G], i32 [Q,G,2]) ncc_scores and where every pair's NCC map peaks
+//   surface_peaks(surfaces [n,h,w], n_peaks, ry, rx) -> (f32 [n,n_peaks], i32 [n,n_peaks], f32 [n])  separated peaks and PSR
 // This file is plain host C++ (no device code): every operator checks its tensors, takes PyTorch's CURRENT HIP stream and
 // calls the same extern "C" entry points the ctypes binding (_lib.py) calls, so both routes run the same kernels bit for
 // bit.  Scratch (prepared spectra, workspaces) comes from PyTorch's caching allocator on that stream; plans are cached per
@@ -195,6 +196,25 @@ std::tuple<at::Tensor, at::Tensor> topk(const at::Tensor& scores, int64_t k) {
   check(spr_topk_rows(scores.data_ptr<float>(), scores.size(1), scores.size(0), scores.size(1), nullptr, 0, static_cast<int32_t>(k),
                       out_scores.data_ptr<float>(), out_index.data_ptr<int32_t>(), current_stream(scores)), "topk");
   return {out_scores, out_index};
+}
+
+// the peaks[n_peaks] best separated peaks of every surface [n, h, w] and the peak-to-sidelobe ratio of the first
+// (spr_surface_peaks): values f32 [n, n_peaks], packed positions i32 [n, n_peaks] ((y << 16) | x, -1 = none), psr f32 [n]
+std::tuple<at::Tensor, at::Tensor, at::Tensor> surface_peaks(const at::Tensor& surfaces, int64_t n_peaks, int64_t ry, int64_t rx) {
+  check_device_tensor(surfaces, "surfaces");
+  TORCH_CHECK(surfaces.dim() == 3 && surfaces.scalar_type() == at::kFloat, "surfaces is a float32 [n, h, w] batch");
+  TORCH_CHECK(n_peaks >= 1 && n_peaks <= 8, "n_peaks = ", n_peaks, " outside [1, 8]");
+  TORCH_CHECK(ry >= 0 && rx >= 0 && ry <= 0x7fffffff && rx <= 0x7fffffff, "the window (", ry, ", ", rx, ") is negative or beyond int32");
+  const DeviceGuard guard(surfaces.device());
+  const int64_t n = surfaces.size(0);
+  at::Tensor values = at::empty({n, n_peaks}, surfaces.options());
+  at::Tensor yx = at::empty({n, n_peaks}, surfaces.options().dtype(at::kInt));
+  at::Tensor psr = at::empty({n}, surfaces.options());
+  if (n == 0) return {values, yx, psr};
+  check(spr_surface_peaks(surfaces.data_ptr<float>(), n, static_cast<int32_t>(surfaces.size(1)), static_cast<int32_t>(surfaces.size(2)),
+                          static_cast<int32_t>(n_peaks), static_cast<int32_t>(ry), static_cast<int32_t>(rx), values.data_ptr<float>(),
+                          yx.data_ptr<int32_t>(), psr.data_ptr<float>(), current_stream(surfaces)), "surface_peaks");
+  return {values, yx, psr};
 }
 
 // the plan cache of `extract` and `extract_taps` (plain VGGs)
@@ -397,6 +417,7 @@ TORCH_LIBRARY(shoeprint_mi355x, m) {
   m.def("extract(Tensor images, Tensor packed, int arch, int block, float[] mean, float[] std, int compute=0) -> Tensor");
   m.def("topk(Tensor scores, int k) -> (Tensor, Tensor)");
   m.def("ncc_scores_located(Tensor q, Tensor g, int crop=2, str method='auto', int max_prepared_bytes=0) -> (Tensor, Tensor)");
+  m.def("surface_peaks(Tensor surfaces, int n_peaks, int ry, int rx) -> (Tensor, Tensor, Tensor)");
 }
 
 // Backend-independent registration: the operators check for GPU tensors themselves (there is no CPU kernel to dispatch to).
@@ -407,4 +428,5 @@ TORCH_LIBRARY_IMPL(shoeprint_mi355x, CompositeExplicitAutograd, m) {
   m.impl("extract_taps", &extract_taps);
   m.impl("topk", &topk);
   m.impl("ncc_scores_located", &ncc_scores_located);
+  m.impl("surface_peaks", &surface_peaks);
 }

@@ -69,6 +69,8 @@ class _Plan:
         self.has_peaks = bool(lib.spr_ncc_plan_has_peaks(handle))
         # spr_ncc_score_list: FFT plans whose working set lies in LDS, and direct plans
         self.has_list = bool(lib.spr_ncc_plan_has_list(handle))
+        # spr_ncc_score_surfaces: exactly the plans that have the list form
+        self.has_surfaces = bool(lib.spr_ncc_plan_has_surfaces(handle))
 
     def close(self):
         if self.handle:
@@ -239,6 +241,54 @@ class NccScorer:
                                                    self.dev.ptr(pairs), n_pairs, self.dev.ptr(scores), self.dev.ptr(peaks),
                                                    None if tags is None else self.dev.ptr(tags),
                                                    1 if accumulate_max else 0, int(tag), self.dev.stream()))
+
+    def surfaces_prepared(self, plan: _Plan, pq, nq: int, pg, ng: int, pairs, n_pairs: int, scores, peaks, surfaces,
+                          tags=None, accumulate_max: bool = False, tag: int = 0):
+        """spr_ncc_score_surfaces: ``score_list_prepared`` that also stores every entry's channel-mean NCC map into
+        ``surfaces`` (device float32 [n_pairs, ih, iw], the cropped gallery map's size) wherever it writes the entry's
+        (score, peak, tag).  Plans without the form (``plan.has_surfaces``): SprError."""
+        self.lib.check(self.lib.spr_ncc_score_surfaces(plan.handle, self.dev.ptr(pq), nq, self.dev.ptr(pg), ng,
+                                                       self.dev.ptr(pairs), n_pairs, self.dev.ptr(scores), self.dev.ptr(peaks),
+                                                       None if tags is None else self.dev.ptr(tags), self.dev.ptr(surfaces),
+                                                       1 if accumulate_max else 0, int(tag), self.dev.stream()))
+
+    def surface_peaks_device(self, surfaces, n_peaks: int = 2, ry: int = 0, rx: int = 0):
+        """spr_surface_peaks of the device float32 [n, h, w] ``surfaces``: device (values float32 [n, n_peaks], packed
+        positions int32 [n, n_peaks] - ``(y << 16) | x``, -1 = no pixel left -, psr float32 [n]).  Peak j is the maximum
+        outside the windows ``|y - y_i| <= ry and |x - x_i| <= rx`` of the peaks before it; psr is the peak-to-sidelobe
+        ratio of peak 0 over the pixels outside its window."""
+        n, h, w = self.dev.shape(surfaces)
+        n_peaks = int(n_peaks)
+        _require_contiguous(surfaces, "surfaces")
+        if n > 0 and self._torch_ops() is not None:
+            return self._torch_ops().surface_peaks(surfaces, n_peaks, int(ry), int(rx))
+        values = self.dev.empty((max(n, 1), max(n_peaks, 1)), np.float32)
+        yx = self.dev.empty((max(n, 1), max(n_peaks, 1)), np.int32)
+        psr = self.dev.empty((max(n, 1),), np.float32)
+        self.lib.check(self.lib.spr_surface_peaks(self.dev.ptr(surfaces), n, h, w, n_peaks, int(ry), int(rx),
+                                                  self.dev.ptr(values), self.dev.ptr(yx), self.dev.ptr(psr), self.dev.stream()))
+        return self.dev.narrow0(values, 0, n), self.dev.narrow0(yx, 0, n), self.dev.narrow0(psr, 0, n)
+
+    def mean_maps_device(self, plan: _Plan, pq, pg, slots, max_bytes: int = 256 << 20) -> np.ndarray:
+        """Host float32 [P, ih, iw] channel-mean NCC maps of the pairs ``slots`` of one plan - the route of plans without a
+        surfaces form: spr_ncc_maps of every pair as in ``peaks_device``, then ONE spr_maps_mean launch per chunk.  The
+        maximum of a map has the bits of ``peaks_device``'s score."""
+        ih, iw = plan.g_hw[0] - 2 * plan.crop, plan.g_hw[1] - 2 * plan.crop
+        per = plan.channels * ih * iw * 4
+        out = np.zeros((len(slots), ih, iw), np.float32)
+        step = max(1, min(len(slots), max_bytes // per))
+        for s0 in range(0, len(slots), step):
+            part = slots[s0:s0 + step]
+            maps = self.dev.zeros((len(part), plan.channels, ih, iw), np.float32)  # (channels dead on either side stay 0)
+            for k, (qp, gp) in enumerate(part):
+                self.lib.check(self.lib.spr_ncc_maps(plan.handle, self.dev.ptr(pq) + qp * plan.query_item_bytes,
+                                                     self.dev.ptr(pg) + gp * plan.gallery_item_bytes,
+                                                     self.dev.ptr(maps) + k * per, self.dev.stream()))
+            mean = self.dev.empty((len(part), ih, iw), np.float32)
+            self.lib.check(self.lib.spr_maps_mean(self.dev.ptr(maps), len(part), plan.channels, ih, iw, self.dev.ptr(mean),
+                                                  self.dev.stream()))
+            out[s0:s0 + len(part)] = self.dev.to_host(mean)
+        return out
 
     def gallery_chunk_items(self, plan: _Plan, n_gallery: int, share: int = 1) -> int:
         """Gallery items per prepared chunk; ``share`` = how many prepared forms of the chunk are alive at once (one per
@@ -460,6 +510,22 @@ class NccScorer:
         and every variant is one spr_ncc_score_list call.  A block one of whose plans has no list form (``plan.has_list``)
         is scored densely, as ``_walk_device`` scores it, and its listed cells are gathered (``cells_device``); where it has
         no peak form either, variant and position come from the second pass of ``locate``, as in ``_fill_unfused``."""
+        return self._score_pairs(shoemark_maps, shoeprint_maps, pairs, rotations, scales, None)
+
+    def pair_surfaces(self, shoemark_maps, shoeprint_maps, pairs, rotations=None, scales=None):
+        """``score_pairs`` with every pair's correlation surface: ``(score, variant, peak_yx, t_hw, surfaces)``, the first
+        four bit for bit ``score_pairs``', ``surfaces`` a list of host float32 [ih, iw] arrays, one per pair (prints are
+        ragged) - the channel-mean NCC map of the winning variant over the cropped gallery map, the map ``peak_yx`` is the
+        arg-max of; all zeros where no variant rises above 0 (variant -1).  The same walk, variant order and tags as
+        ``score_pairs``, one spr_ncc_score_surfaces call per variant through accumulate_max: the device buffer ends with the
+        winning variant's map.  A block one of whose plans lacks the form (``plan.has_surfaces``: the matrix-core methods,
+        the workspace instance) takes its triple as ``score_pairs`` does; its maps are spr_ncc_maps of the winning variant
+        folded by spr_maps_mean (float64 channel sums: the maximum has the bits of ``locate``'s score)."""
+        surfaces: list = [None] * len(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+        return (*self._score_pairs(shoemark_maps, shoeprint_maps, pairs, rotations, scales, surfaces), surfaces)
+
+    def _score_pairs(self, shoemark_maps, shoeprint_maps, pairs, rotations, scales, surfaces):
+        """``score_pairs``; with ``surfaces`` (a list of one slot per pair) also ``pair_surfaces``' maps, written into it."""
         dev = self.dev
         q_items, g_items = _side(dev, shoemark_maps), _side(dev, shoeprint_maps)
         pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
@@ -474,6 +540,7 @@ class NccScorer:
             raise IndexError("a pair names an item outside the query or gallery set")
         q_used, g_used = (sorted({int(i) for i in pairs[:, side]}) for side in (0, 1))
         unlocated = []  # entries of blocks without a peak form
+        unmapped = []   # ``surfaces``: entries of blocks without a surfaces form
         for b in self._blocks(q_items, g_items, rotations, scales, q_used, g_used):
             q_pos = np.full(len(q_items), -1, dtype=np.int64)
             g_pos = np.full(len(g_items), -1, dtype=np.int64)
@@ -493,12 +560,23 @@ class NccScorer:
                 sub = dev.zeros((len(sel),), np.float32)
                 sub_yx = dev.to_device(np.full(len(sel), -1, dtype=np.int32))
                 sub_tag = dev.to_device(np.full(len(sel), -1, dtype=np.int32))
+                maps = None
+                if surfaces is not None:  # (one map shape per block: the gallery class's; entries no variant wins stay 0)
+                    g_hw = b.plans[b.variants[0][1]].g_hw
+                    maps = dev.zeros((len(sel), g_hw[0] - 2 * self.crop, g_hw[1] - 2 * self.crop), np.float32)
                 for number, vs, v in b.variants:
                     plan = b.plans[vs]
                     pg = b.prepared(vs)
-                    self.score_list_prepared(plan, self.prepare_queries(plan, v), nq_b, pg, ng_b, listed, len(sel), sub, sub_yx,
-                                             sub_tag, accumulate_max=True, tag=number)
+                    if maps is None:
+                        self.score_list_prepared(plan, self.prepare_queries(plan, v), nq_b, pg, ng_b, listed, len(sel), sub,
+                                                 sub_yx, sub_tag, accumulate_max=True, tag=number)
+                    else:
+                        self.surfaces_prepared(plan, self.prepare_queries(plan, v), nq_b, pg, ng_b, listed, len(sel), sub,
+                                               sub_yx, maps, sub_tag, accumulate_max=True, tag=number)
                 got = (dev.to_host(sub), dev.to_host(sub_tag), dev.to_host(sub_yx))
+                if maps is not None:
+                    for i, m in zip(sel, np.array(dev.to_host(maps))):
+                        surfaces[i] = m
             else:  # the dense route of _walk_device for this block alone, read at the listed cells
                 fused = all(b.plans[vs].has_peaks for _, vs, _ in b.variants)
                 sub = dev.zeros((nq_b, ng_b), np.float32)
@@ -514,6 +592,8 @@ class NccScorer:
                        self.cells_device(sub_yx, ng_b, qs, gs) if fused else np.full(len(sel), -1, dtype=np.int32))
                 if not fused:
                     unlocated.append(sel)
+                if surfaces is not None:
+                    unmapped.append(sel)
             scores[sel], variant[sel], yx[sel] = got[0], got[1], _unpack_yx(got[2])
             hit = got[1] >= 0
             t_hw[sel[hit]] = np.array([sizes[int(number)] for number in got[1][hit]], dtype=np.int32).reshape(-1, 2)
@@ -522,7 +602,32 @@ class NccScorer:
             rest = rest[scores[rest] > 0]  # (as the fused form: no position where the floored score is 0)
             if len(rest):
                 _, variant[rest], yx[rest], t_hw[rest] = self._locate(q_items, g_items, pairs[rest], rotations, scales)
+        if unmapped:
+            self._fill_unmapped(q_items, g_items, pairs, np.concatenate(unmapped), variant, rotations, scales, surfaces)
         return scores, variant, yx, t_hw
+
+    def _fill_unmapped(self, q_items, g_items, pairs, rows, variant, rotations, scales, surfaces) -> None:
+        """``pair_surfaces`` for the entries ``rows`` of blocks without a surfaces form: a second walk over the items they
+        name, and per block and variant the maps (``mean_maps_device``) of the entries that variant won; zeros where none did."""
+        q_used, g_used = (sorted({int(i) for i in pairs[rows, side]}) for side in (0, 1))
+        for b in self._blocks(q_items, g_items, rotations, scales, q_used, g_used):
+            q_pos = {q: i for i, q in enumerate(b.q_idx)}
+            g_pos = {g: i for i, g in enumerate(b.g_idx)}
+            sel = [int(i) for i in rows if int(pairs[i, 0]) in q_pos and int(pairs[i, 1]) in g_pos]
+            if not sel:
+                continue
+            g_hw = b.plans[b.variants[0][1]].g_hw
+            for i in sel:
+                if variant[i] < 0:
+                    surfaces[i] = np.zeros((g_hw[0] - 2 * self.crop, g_hw[1] - 2 * self.crop), np.float32)
+            for number, vs, v in b.variants:
+                won = [i for i in sel if variant[i] == number]
+                if not won:
+                    continue
+                plan = b.plans[vs]
+                slots = [(q_pos[int(pairs[i, 0])], g_pos[int(pairs[i, 1])]) for i in won]
+                for i, m in zip(won, self.mean_maps_device(plan, self.prepare_queries(plan, v), b.prepared(vs), slots)):
+                    surfaces[i] = m
 
     def score_matrix(self, shoemark_maps, shoeprint_maps, accumulate_into=None, rotations=None,
                      scales=None) -> np.ndarray:
@@ -846,13 +951,18 @@ def compare_maps(
 @dataclass
 class Shortlist:
     """What ``retrieve`` returns.  Slot [q, p] is the gallery item ranked p + 1 for query q; slots beyond the gallery size
-    hold index -1 (score 0, and with ``locate``: variant -1, peak_yx (-1, -1), offset (0, 0))."""
+    hold index -1 (score 0, and with ``locate``: variant -1, peak_yx (-1, -1), offset (0, 0)).  The last four fields are
+    filled by ``retrieve(..., surfaces=True)``: what an examiner judges the peak by.  Empty slots hold None / 0 / 0 / -1."""
 
     index: np.ndarray            # int32 [Q,k] gallery index
     score: np.ndarray            # float32 [Q,k] its entry of the score matrix (floored at 0, maximum over variants)
     variant: np.ndarray | None   # int32 [Q,k] number of the best query variant (variants.variant_labels names them)
     peak_yx: np.ndarray | None   # int32 [Q,k,2] peak of that variant's channel-summed NCC map, cropped gallery-map coordinates
     offset: np.ndarray | None    # int32 [Q,k,2] top-left corner of the cropped variant template in the cropped gallery map
+    surface: np.ndarray | None = None         # object [Q,k]: float32 [ih,iw] channel-mean NCC map of the best variant (``pair_surfaces``)
+    psr: np.ndarray | None = None             # float32 [Q,k] peak-to-sidelobe ratio of that map's maximum (spr_surface_peaks)
+    peak_values: np.ndarray | None = None     # float32 [Q,k,peaks] the map's best separated peaks, the maximum first
+    peak_positions: np.ndarray | None = None  # int32 [Q,k,peaks,2] where they lie, (-1, -1) = no pixel left
 
 
 def retrieve(
@@ -863,19 +973,27 @@ def retrieve(
     *,
     locate: bool = True,
     scorer: NccScorer | None = None,
+    surfaces: bool = False,
+    peaks: int = 2,
 ) -> Shortlist:
     """The ``k`` best gallery items of every query (1 <= k <= 256), best first in the ranker's order, and - with
     ``locate`` - for each of them the best query variant, the peak of its NCC map and the offset
     ``(y - th//2, x - tw//2)`` at which the cropped ``th x tw`` variant template lies on the cropped gallery map.
     ``config["comparison"]`` supplies rotations and scales as for ``compare_maps``.  With a ``features.FeatureSet`` on both
-    sides the score matrix never leaves HBM (``retrieve_resident``)."""
+    sides the score matrix never leaves HBM (``retrieve_resident``).  With ``surfaces`` every shortlisted pair also gets
+    its correlation surface (``NccScorer.pair_surfaces``: one more pass over the Q * k pairs), the surface's ``peaks`` best
+    separated peaks (1..8) and the peak-to-sidelobe ratio of its maximum (spr_surface_peaks).  The exclusion window is half
+    the winning variant's cropped template, ``ry = th // 2, rx = tw // 2``: the runner-up is an alignment whose template
+    centre lies outside the best one's footprint.  Everything else is what it is without the keyword, bit for bit."""
+    kw = {"locate": locate, "scorer": scorer, "surfaces": surfaces, "peaks": peaks}
     if _is_resident(shoemark_maps) and _is_resident(shoeprint_maps):
-        return retrieve_resident(shoemark_maps, shoeprint_maps, config, k, locate=locate, scorer=scorer)[1]
-    return retrieve_with_scores(shoemark_maps, shoeprint_maps, config, k, locate=locate, scorer=scorer)[1]
+        return retrieve_resident(shoemark_maps, shoeprint_maps, config, k, **kw)[1]
+    return retrieve_with_scores(shoemark_maps, shoeprint_maps, config, k, **kw)[1]
 
 
 def retrieve_with_scores(shoemark_maps, shoeprint_maps, config: dict, k: int = 10, *, locate: bool = True,
-                         scorer: NccScorer | None = None) -> tuple[np.ndarray, Shortlist]:
+                         scorer: NccScorer | None = None, surfaces: bool = False,
+                         peaks: int = 2) -> tuple[np.ndarray, Shortlist]:
     """``retrieve`` together with the host float32 [Q,G] score matrix it was taken from (what ``score_matrix`` gives for
     these maps and variants, bit for bit): one scoring pass serves ranks of known matches and the shortlist
     (run_mi355x.py).  With ``locate`` the pass is ``score_matrix_located``'s list-of-arrays walk - device-resident
@@ -887,17 +1005,22 @@ def retrieve_with_scores(shoemark_maps, shoeprint_maps, config: dict, k: int = 1
     rotations, scales = comp.get("rotations"), comp.get("scales")
     scorer = scorer or scorer_from_config(config)
     if _is_resident(shoemark_maps) and _is_resident(shoeprint_maps):
-        s_dev, short = retrieve_resident(shoemark_maps, shoeprint_maps, config, k, locate=locate, scorer=scorer)
+        s_dev, short = retrieve_resident(shoemark_maps, shoeprint_maps, config, k, locate=locate, scorer=scorer,
+                                         surfaces=surfaces, peaks=peaks)
         return scorer.dev.to_host(s_dev), short
     if not locate:
         scores = scorer.score_matrix(shoemark_maps, shoeprint_maps, rotations=rotations, scales=scales)
-        return scores, _shortlist(scorer, shoemark_maps, shoeprint_maps, scores, k, False, rotations, scales)
-    scores, *located = scorer._score_matrix_located(shoemark_maps, shoeprint_maps, rotations, scales, fill_unfused=False)
-    return scores, _shortlist(scorer, shoemark_maps, shoeprint_maps, scores, k, True, rotations, scales, located=located)
+        short = _shortlist(scorer, shoemark_maps, shoeprint_maps, scores, k, False, rotations, scales)
+    else:
+        scores, *located = scorer._score_matrix_located(shoemark_maps, shoeprint_maps, rotations, scales, fill_unfused=False)
+        short = _shortlist(scorer, shoemark_maps, shoeprint_maps, scores, k, True, rotations, scales, located=located)
+    if surfaces:
+        _add_surfaces(scorer, short, shoemark_maps, shoeprint_maps, rotations, scales, peaks)
+    return scores, short
 
 
 def retrieve_resident(shoemark_maps, shoeprint_maps, config: dict, k: int = 10, *, locate: bool = True,
-                      scorer: NccScorer | None = None):
+                      scorer: NccScorer | None = None, surfaces: bool = False, peaks: int = 2):
     """``retrieve_with_scores`` for ``features.FeatureSet``s that leaves the matrix where it is: (device float32 [Q,G]
     scores, Shortlist).  The top k are taken from the device matrix and the shortlisted entries' variant and position are
     gathered from the device matrices; what comes down is the Shortlist's own arrays (and ``locate``'s per-pair results for
@@ -907,11 +1030,43 @@ def retrieve_resident(shoemark_maps, shoeprint_maps, config: dict, k: int = 10, 
     scorer = scorer or scorer_from_config(config)
     if not locate:
         s_dev = scorer.score_matrix_device(shoemark_maps, shoeprint_maps, rotations, scales)
-        return s_dev, _shortlist(scorer, shoemark_maps, shoeprint_maps, s_dev, k, False, rotations, scales, resident=True)
-    q_items, g_items = _side(scorer.dev, shoemark_maps), _side(scorer.dev, shoeprint_maps)
-    s_dev, *located = scorer._walk_device(q_items, g_items, rotations, scales, True)[:4]  # (unfused blocks: not filled)
-    return s_dev, _shortlist(scorer, shoemark_maps, shoeprint_maps, s_dev, k, True, rotations, scales, located=located,
-                             resident=True)
+        short = _shortlist(scorer, shoemark_maps, shoeprint_maps, s_dev, k, False, rotations, scales, resident=True)
+    else:
+        q_items, g_items = _side(scorer.dev, shoemark_maps), _side(scorer.dev, shoeprint_maps)
+        s_dev, *located = scorer._walk_device(q_items, g_items, rotations, scales, True)[:4]  # (unfused blocks: not filled)
+        short = _shortlist(scorer, shoemark_maps, shoeprint_maps, s_dev, k, True, rotations, scales, located=located,
+                           resident=True)
+    if surfaces:
+        _add_surfaces(scorer, short, shoemark_maps, shoeprint_maps, rotations, scales, peaks)
+    return s_dev, short
+
+
+def _add_surfaces(scorer: NccScorer, short: Shortlist, shoemark_maps, shoeprint_maps, rotations, scales, peaks: int) -> None:
+    """The four surface fields of a shortlist: ``pair_surfaces`` of its entries, then spr_surface_peaks per map shape and
+    exclusion window (half the winning variant's cropped template).  Nothing else of ``short`` is touched."""
+    if isinstance(peaks, bool) or int(peaks) != peaks or not 1 <= int(peaks) <= 8:
+        raise ValueError(f"peaks = {peaks!r}: expected an integer in [1, 8]")
+    peaks = int(peaks)
+    dev = scorer.dev
+    nq, kk = short.index.shape
+    short.surface = np.full((nq, kk), None, dtype=object)
+    short.psr = np.zeros((nq, kk), dtype=np.float32)
+    short.peak_values = np.zeros((nq, kk, peaks), dtype=np.float32)
+    short.peak_positions = np.full((nq, kk, peaks, 2), -1, dtype=np.int32)
+    qs, ps = np.nonzero(short.index >= 0)
+    if len(qs) == 0:
+        return
+    *_, t_hw, maps = scorer.pair_surfaces(shoemark_maps, shoeprint_maps, np.stack([qs, short.index[qs, ps]], axis=1),
+                                          rotations=rotations, scales=scales)
+    groups: dict[tuple, list[int]] = {}
+    for i, m in enumerate(maps):
+        short.surface[qs[i], ps[i]] = m
+        groups.setdefault((m.shape, int(t_hw[i, 0]) // 2, int(t_hw[i, 1]) // 2), []).append(i)
+    for (_, ry, rx), rows in groups.items():
+        values, yx, psr = scorer.surface_peaks_device(dev.to_device(np.stack([maps[i] for i in rows])), peaks, ry, rx)
+        short.peak_values[qs[rows], ps[rows]] = dev.to_host(values)
+        short.peak_positions[qs[rows], ps[rows]] = _unpack_yx(dev.to_host(yx))
+        short.psr[qs[rows], ps[rows]] = dev.to_host(psr)
 
 
 def _shortlist(scorer: NccScorer, shoemark_maps, shoeprint_maps, scores, k: int, locate: bool, rotations,
@@ -971,14 +1126,20 @@ class Cascade:
     peak_yx: np.ndarray          # int32 [Q,M,2] peak of that variant's NCC map, cropped gallery-map coordinates of that layer
     offset: np.ndarray           # int32 [Q,M,2] top-left corner of the cropped variant template in the cropped gallery map
     scorer: Any = None
+    located: Any = None          # (query set, gallery set, rotations, scales) of the located layer: ``shortlist(surfaces=True)``
 
-    def shortlist(self, k: int) -> Shortlist:
-        """The first ``k`` columns (1 <= k <= M) as ``retrieve`` lays them out."""
+    def shortlist(self, k: int, *, surfaces: bool = False, peaks: int = 2) -> Shortlist:
+        """The first ``k`` columns (1 <= k <= M) as ``retrieve`` lays them out.  With ``surfaces`` the four surface fields
+        of ``retrieve(..., surfaces=True)``, on the located layer."""
         if not 1 <= int(k) <= self.index.shape[1]:
             raise ValueError(f"k = {k}: the cascade holds {self.index.shape[1]} candidates per query")
         k = int(k)
-        return Shortlist(self.index[:, :k].copy(), self.score[:, :k].copy(), self.variant[:, :k].copy(),
-                         self.peak_yx[:, :k].copy(), self.offset[:, :k].copy())
+        short = Shortlist(self.index[:, :k].copy(), self.score[:, :k].copy(), self.variant[:, :k].copy(),
+                          self.peak_yx[:, :k].copy(), self.offset[:, :k].copy())
+        if surfaces:
+            q, g, rotations, scales = self.located
+            _add_surfaces(self.scorer, short, q, g, rotations, scales, peaks)
+        return short
 
     def ranks(self, matching_pairs: Sequence[int]) -> np.ndarray:
         """int32 [Q]: the position of query q's match among its re-ranked candidates + 1 where it is one of them, otherwise
@@ -1030,7 +1191,8 @@ def retrieve_cascade(layer_sets, config: dict, depth: int, *, coarse: int = -1, 
         if (len(_side(dev, q)), len(_side(dev, g))) != (nq, ng):
             raise ValueError(f"layer {k} holds {len(_side(dev, q))} x {len(_side(dev, g))} items, the coarse layer {nq} x {ng}")
     out = Cascade(coarse_scores, np.full((nq, m), -1, np.int32), np.zeros((nq, m), np.float32), np.full((nq, m), -1, np.int32),
-                  np.full((nq, m, 2), -1, np.int32), np.zeros((nq, m, 2), np.int32), scorer)
+                  np.full((nq, m, 2), -1, np.int32), np.zeros((nq, m, 2), np.int32), scorer,
+                  (*layer_sets[locate_layer], rotations, scales))
     if nq == 0:
         return out
     top_s, top_i = scorer.topk_device(coarse_scores, m)
